@@ -12,7 +12,15 @@ max over ranks.
 Multi-GPU: the path shards by image with no exchange step ("replicas only"): every
 rank runs its own bs=2 batch; RCCL is used only for the barrier and the max-over-ranks of the time.
 
+A plain run sets up, warms up, times the K steps and prints the one JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step, ...).  --full adds the separate
+measurements outside the timed region: calibration, per-kernel roofline, the other precisions, the
+concurrency probe, the serial_* reference point and the CPU oracle baseline.  --dump-outputs DIR
+writes the outputs of the last timed step as DIR/<name>.npy (seeded inputs: the same in every run
+with the same arguments, so two builds can be compared output for output).
+
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -116,7 +124,62 @@ def parse():
     ap.add_argument("--dry-launch", action="store_true",
                     help="--gpus N without a torchrun environment: spawn the N ranks, have each print its RANK / LOCAL_RANK / "
                          "WORLD_SIZE and exit before anything touches a GPU (launcher test)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure, as separate measurements outside the timed region: the "
+                         "calibration (calib / value_normalised), the per-kernel event profile (roofline / kernels), the "
+                         "other 16-bit type and f32 (alt_dtype), the pipeline concurrency probe, the serial_* reference "
+                         "point and the CPU oracle baseline (cpu_baseline); the --no-* switches above still drop single "
+                         "items.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed to its caller as DIR/<name>.npy "
+                         "(float32, float64 for float64 / integer outputs; at most 64 MB in all, larger outputs as a fixed "
+                         "seeded sample of their elements); rank 0 only")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def _named_arrays(obj, name, out):
+    """Tensors / numbers of a step's result, depth first, as {name: tensor}; containers add "_<index or key>"."""
+    if torch.is_tensor(obj):
+        out[name] = obj
+    elif isinstance(obj, (bool, int, float)):
+        out[name] = torch.tensor(obj, dtype=torch.float64)
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            _named_arrays(v, f"{name}_{k}", out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _named_arrays(v, f"{name}_{i}", out)
+    return out
+
+
+def host_outputs(result, name="out"):
+    """Host copies (float32, or float64 for float64 / integer tensors) of every tensor in a step's result -- taken right
+    after the timed region, before anything else runs on the device (the runners' output buffers are reused)."""
+    out = {}
+    for k, t in _named_arrays(result, name, {}).items():
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        out[k] = t.to("cpu", torch.float64 if wide else torch.float32).contiguous()
+    return out
+
+
+def dump_outputs(arrays, path):
+    """``arrays`` -> path/<name>.npy; above DUMP_LIMIT_BYTES in all, every array is cut to the same fraction of its
+    elements, chosen by a fixed seed (the same positions in every run with the same arguments)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() * t.element_size() for t in arrays.values())
+    frac = min(1.0, DUMP_LIMIT_BYTES / total) if total else 1.0
+    for k, t in arrays.items():
+        if frac < 1.0:
+            flat = t.flatten()
+            keep = max(1, int(flat.numel() * frac))
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = flat[idx]
+        np.save(os.path.join(path, k + ".npy"), t.numpy())
 
 
 def make_inputs(B, size, device, seed=0):
@@ -206,6 +269,8 @@ def run_train(args, rank, world, device, dist, mdist):
         losses, norm, stepped = trainer.run_step(data)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(host_outputs({"losses": losses, "grad_norm": norm}, "train"), args.dump_outputs)
     if dist is not None:
         dist.barrier()
         elapsed = mdist.max_over_ranks(elapsed, dist, device)
@@ -449,11 +514,11 @@ def run(args, model, call, ldm, rank, world, device, dist, mdist, pool):
     torch.cuda.synchronize()
 
     calib = None
-    if rank == 0 and args.workload == "extract" and args.dtype in ("f16", "bf16") and not args.no_calib:
+    if args.full and rank == 0 and args.workload == "extract" and args.dtype in ("f16", "bf16") and not args.no_calib:
         # before the warm-up and the timed region: a kernel trace of this process ends with the step's own launches
         calib = calibrate(device, {"bf16": torch.bfloat16, "f16": torch.float16}[args.dtype])
     prof = layers = None
-    if rank == 0 and not args.no_kernel_profile:
+    if args.full and rank == 0 and not args.no_kernel_profile:
         prof, layers = kernel_profile(model, call)
 
     first_stream = None      # set when the steps run on streams of their own
@@ -561,7 +626,7 @@ def run(args, model, call, ldm, rank, world, device, dist, mdist, pool):
     serial_ms = None
     if graphed:
         serial_ms = None          # measured after the timed region on a whole-forward graph of a synchronous forward() (below)
-    elif not args.no_graph and not staged and args.streams > 1:
+    elif args.full and not args.no_graph and not staged and args.streams > 1:
         serial_ms = serial_reference(graphs[0], streams[0])
     if dist is not None:
         dist.barrier()
@@ -580,11 +645,12 @@ def run(args, model, call, ldm, rank, world, device, dist, mdist, pool):
     if single:
         ev0.record()
     for i in range(args.steps):
-        step(args.warmup + i)
+        last = step(args.warmup + i)
     if single:
         ev1.record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = host_outputs(last) if args.dump_outputs and rank == 0 and args.steps > 0 else None
     if dist is not None:
         dist.barrier()
         elapsed = mdist.max_over_ranks(elapsed, dist, device)
@@ -595,7 +661,7 @@ def run(args, model, call, ldm, rank, world, device, dist, mdist, pool):
             range_checked = runner.range_check.checked
     alt = None
     conc = None
-    if staged:
+    if staged and args.full:
         conc = pipe.concurrency_probe()
         if world == 1 and args.dtype in ("f16", "bf16") and not args.no_alt_dtype and not args.lora:
             # configs[1] says bf16, the default arithmetic is f16 (the reference's autocast type): the other 16-bit type is
@@ -634,7 +700,7 @@ def run(args, model, call, ldm, rank, world, device, dist, mdist, pool):
                 torch.cuda.empty_cache()
         gs_, _, sts_ = capture_whole_forward(1, 1)
         serial_ms = serial_reference(gs_[0], sts_[0])
-    elif graphed:
+    elif graphed and args.full:
         # one image in flight: the whole-forward graph of a synchronous model(batched_inputs) call -- captured under the latency
         # profile of the tile table (ops.sync_profile), unlike the runner's graphs
         gs_, _, sts_ = capture_whole_forward(1, 1)
@@ -652,25 +718,29 @@ def run(args, model, call, ldm, rank, world, device, dist, mdist, pool):
                + ("in PINNED HOST memory: PCIe-inclusive, informational" if getattr(args, "host_inputs", False) else "resident in HBM")
                + ") through "
                "{}.submit(batched_inputs): the inputs are copied into the slot's static buffers on the device per step")
+        # the serial_* fields are measured with --full only: their description goes with them
+        serial = (lambda what: "; serial_* = " + what) if serial_ms is not None else (lambda what: "")
         if args.no_graph:
             launch = "eager launches, a different seeded batch per step"
         elif staged:
             launch = (f"staged hipGraph pipeline (madm_amd/pipeline.py): VAE-encoder graphs on 1 stream, UNet graphs on "
                       f"{args.pipeline} streams, {pipe.n_slots} slots, up to {pipe.n_slots + 1} batches ({(pipe.n_slots + 1) * args.batch} images) in "
                       f"flight, GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES', 'default')}; "
-                      + fed.format("StagedExtractor") + "; serial_* = whole-forward graph of a synchronous forward() (the "
-                      "latency profile of the tile table: lone-launch rows), one batch in flight")
+                      + fed.format("StagedExtractor") + serial("whole-forward graph of a synchronous forward() (the "
+                                                               "latency profile of the tile table: lone-launch rows), one "
+                                                               "batch in flight"))
         elif graphed:
             launch = (f"three stage graphs per image (madm_amd/pipeline.py::StagedInference): VAE encoder | UNet on {runner.k} streams | "
                       f"VAE decoder + projections + head, {runner.n_slots} slots; " + fed.format("StagedInference")
                       ) if args.eval_runner == "staged" else (
                       f"whole-forward hipGraphs (madm_amd/pipeline.py::GraphedInference) on {max(1, args.streams)} streams: "
                       f"{max(1, args.streams)} images in flight; " + fed.format("GraphedInference")
-                      + "; serial_* = one image in flight (whole-forward graph of a synchronous call: latency profile of the tile table)")
+                      + serial("one image in flight (whole-forward graph of a synchronous call: latency profile of the tile "
+                               "table)"))
         else:
             launch = ("hipGraph replay of ONE captured batch, 1 stream: one batch in flight" if args.streams <= 1 else
-                      f"hipGraph replay of ONE captured batch on {args.streams} streams: {args.streams} batches in flight; "
-                      "serial_* = one batch in flight") + " (reference / profiling mode, not the product runner)"
+                      f"hipGraph replay of ONE captured batch on {args.streams} streams: {args.streams} batches in flight"
+                      + serial("one batch in flight")) + " (reference / profiling mode, not the product runner)"
         if runner is not None and runner.range_check is not None:
             rc = (f"deferred, on: the reference's per-call input-range assert (ldm_diffusers.py:147) is kept inside the timed "
                   f"region without its host sync -- every step's min / max probe is copied to pinned memory behind the encoder "
@@ -750,8 +820,10 @@ def run(args, model, call, ldm, rank, world, device, dist, mdist, pool):
             out["kernels"] = {k: {"launches": v[0], "ms": round(v[4], 4), "ms_events_raw": round(v[1], 4),
                                   "tflops": round(v[2] / (v[4] * 1e-3) / 1e12, 2) if v[4] > 0 else None}
                               for k, v in sorted(prof.items(), key=lambda kv: -kv[1][4])}
-        if world == 1 and not args.no_cpu_baseline and args.workload == "extract":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "extract":
             out["cpu_baseline"] = cpu_baseline(args.size)
+        if dumped is not None:
+            dump_outputs(dumped, args.dump_outputs)
         emit(out)
     if dist is not None:
         dist.destroy_process_group()

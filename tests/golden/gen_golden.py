@@ -4,7 +4,8 @@
 oracle modules (oracle/sd_modules.py) filled with seeded synthetic parameters (madm_amd/weights.py).
 Inputs are regenerated from seeds by the tests (``make_inputs``); only outputs are stored.
 
-    python tests/golden/gen_golden.py            # writes tests/golden/*.npz
+    python tests/golden/gen_golden.py            # writes tests/golden/*.npz and reference_names.json
+    python tests/golden/gen_golden.py pins       # only reference_pins.npz / reference_names.json (main_pins)
 """
 import os
 import sys
@@ -246,8 +247,90 @@ def main_labels():
     print("labels.npz", {k: getattr(v, "shape", v) for k, v in out.items()})
 
 
+def main_pins():
+    """Everything else the CPU tests compare with the reference's OWN code, recorded so that they need no reference
+    checkout: the 'ldm_linear' schedule of modeling/diffusion, the orchestration functions on an encoder tap / 'in' taps /
+    t = 60, CmdiseCriterion's losses and gradients, the state_dict() names and shapes of the reference-class models, the
+    parameters its dummy-backward procedure (ldm_diffusers.py:123-141) leaves without gradient.  Tensors ->
+    reference_pins.npz, names -> reference_names.json."""
+    import importlib.util
+    import json
+    from copy import deepcopy
+    from oracle import madm_path, train_path
+    from golden_util import criterion_inputs, UNUSED_PARAM_CASES, unused_param_inputs
+    ref_root = os.path.dirname(os.path.dirname(train_path.REF_CRITERION))
+    pins, names = {}, {}
+    # K4: the schedule in float64
+    spec = importlib.util.spec_from_file_location("_ref_gd", os.path.join(ref_root, "modeling/diffusion/gaussian_diffusion.py"))
+    gd = importlib.util.module_from_spec(spec)
+    sys.modules["_ref_gd"] = gd
+    spec.loader.exec_module(gd)
+    pins["alphas_cumprod"] = np.cumprod(1.0 - gd.get_named_beta_schedule("ldm_linear", 1000))
+    # vae_encoder with an encoder tap, add_noise at t = 60, diffusion_unet with 'after' and 'in' taps, vae_decoder
+    ref = ref_driver.load()
+    vae, unet = build_oracle(lora=False)
+    sched = sd_modules.DDPMScheduler()
+    images, cond_inputs, cond_emb, timesteps, shared_noise = make_inputs(2, 64, 64, 60, 0.02)
+    with torch.no_grad():
+        la, fa = ref.vae_encoder(vae=vae, images=(images - 0.5) / 0.5, encoder_block_indices=[5])
+        na = ref.add_noise(noise_scheduler=sched, latents=la, timesteps=timesteps, shared_noise=shared_noise)
+        pins.update(latents=la, enc_tap5=fa[0][:, ::CH_STRIDE_FULL], noisy=na)
+        for typ, idxs in (("after", [5, 8, 11]), ("in", [0, 6, 11])):
+            oa, ta = ref.diffusion_unet(unet=unet, sample=na, timestep=timesteps, encoder_hidden_states=cond_inputs,
+                                        res_time_embedding=cond_emb.clone(), unet_block_indices=idxs,
+                                        unet_block_indices_type=typ)
+            pins[f"{typ}_sample"] = oa.sample
+            for i, t in enumerate(ta):
+                pins[f"{typ}_tap{i}"] = t[:, ::CH_STRIDE_FULL]
+                pins[f"{typ}_tap{i}_shape"] = np.array(t.shape, dtype=np.int64)
+        pins["decoder"], _ = ref.vae_decoder(vae=vae, latents=la, decoder_block_indices=[], output_final=True)
+    pins["enc_tap5_shape"] = np.array(fa[0].shape, dtype=np.int64)
+    # CmdiseCriterion (modeling/criterion.py:110-254): losses and the gradients of the three differentiable inputs
+    sp, tp_, pred, tgt = criterion_inputs()
+    losses = train_path.reference_criterion()(loss_weight=1.0)({'source_rgb_pred': sp, 'target_sec_modal_pred': tp_}, tgt)
+    sum(losses.values()).backward()
+    for k, v in losses.items():
+        pins["criterion_" + k] = v.detach().double()
+    pins.update(criterion_grad_source=sp.grad, criterion_grad_target=tp_.grad, criterion_grad_pred=pred.grad)
+    # state_dict() names / shapes of the reference-class eval model and of the meta-architecture a checkpoint loads into
+    shapes = lambda sd: {k: list(v.shape) for k, v in sd.items()}
+    ns = ref_driver.load_modeling()
+    rb, rh = madm_path.build_reference_eval_model(ns, vae, unet, madm_path.DEPTH_CFG)
+    names["eval_model_depth"] = {"backbone": {k: s for k, s in shapes(rb.state_dict()).items() if "ldm_extractor" not in k},
+                                 "head": shapes(rh.state_dict()), "size_divisibility": rb.size_divisibility,
+                                 "out_features": list(rb._out_features)}
+    meta = torch.nn.Module()
+    meta.backbone, meta.sem_seg_head = rb, rh
+    meta.sem_seg_head_sec_modal = rh                       # cmdise.py:153-156: the same object under a second name
+    # CMDISE._inti_ema_weights (cmdise.py:307-335)
+    meta.backbone.ema_feature_projections = deepcopy(rb.feature_projections)
+    meta.ema_sem_seg_head = deepcopy(rh)
+    meta.backbone.feature_extractor.ema_clip_project_others = deepcopy(rb.feature_extractor.clip_project_others)
+    names["meta_arch_depth"] = shapes(meta.state_dict())
+    # parameters without gradient after the reference's dummy backward, per tap set
+    names["unused_params"] = {}
+    for taps, kind in UNUSED_PARAM_CASES:
+        for p in unet.parameters():
+            p.requires_grad = True
+            p.grad = None
+        sample, ctx = unused_param_inputs()
+        _, feats = ref.diffusion_unet(unet=unet, sample=sample, timestep=torch.zeros(1).long(), encoder_hidden_states=ctx,
+                                      res_time_embedding=None, unet_block_indices=taps, unet_block_indices_type=kind)
+        torch.nn.functional.mse_loss(input=feats[-1], target=torch.ones_like(feats[-1])).backward()
+        names["unused_params"][f"{kind}:{','.join(map(str, taps))}"] = sorted(
+            n for n, p in unet.named_parameters() if p.grad is None)
+    np.savez_compressed(os.path.join(HERE, "reference_pins.npz"),
+                        **{k: v.numpy() if torch.is_tensor(v) else v for k, v in pins.items()})
+    with open(os.path.join(HERE, "reference_names.json"), "w") as f:
+        json.dump(names, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("reference_pins.npz", {k: tuple(v.shape) for k, v in pins.items()})
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if not args or "pins" in args:
+        main_pins()
     if not args or any(a.startswith("train_") for a in args):
         main_train()
     if not args or "labels" in args:

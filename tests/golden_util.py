@@ -190,6 +190,36 @@ def fixture_decision_margins(gold, size, pseudo_threshold):
     return top[:, 0] - top[:, 1], (top[:, 0] - pseudo_threshold).abs()
 
 
+def criterion_inputs():
+    """Seeded logits / labels / weights / latents of the criterion pin (tests/golden/reference_pins.npz criterion_*):
+    (source logits, target logits, decoder prediction) as fresh leaf tensors, and the targets dict."""
+    B, K, h, H = 2, 11, 16, 64
+    sp = torch.randn((B, K, h, h), generator=torch.Generator().manual_seed(1)).requires_grad_(True)
+    tp_ = torch.randn((B, K, h, h), generator=torch.Generator().manual_seed(2)).requires_grad_(True)
+    pred = torch.randn((B, 4, 8, 8), generator=torch.Generator().manual_seed(3)).requires_grad_(True)
+    gt = torch.randint(0, K, (B, 1, H, H), generator=torch.Generator().manual_seed(4))
+    gt[torch.rand((B, 1, H, H), generator=torch.Generator().manual_seed(5)) < 0.1] = 255
+    tgt = {'source_gt': gt, 'target_pl': gt.flip(0), 'target_pw': torch.rand((B, H, H), generator=torch.Generator().manual_seed(6)),
+           'vae_decoder_loss': {'source': {'pred': pred, 'gt': torch.randn((B, 4, 8, 8), generator=torch.Generator().manual_seed(7)),
+                                           'mask': torch.rand((B, 1, H, H), generator=torch.Generator().manual_seed(8)),
+                                           'loss_weight': 20.0, 'loss_type': 'L1'},
+                                'target': {'pred': pred * 0.5, 'gt': torch.randn((B, 4, 8, 8), generator=torch.Generator().manual_seed(9)),
+                                           'mask': torch.rand((B, 1, H, H), generator=torch.Generator().manual_seed(10)),
+                                           'loss_weight': 1.0, 'loss_type': 'L2'}}}
+    return sp, tp_, pred, tgt
+
+
+# tap sets of the unused-parameter pin (tests/golden/reference_names.json unused_params, keyed "kind:taps")
+UNUSED_PARAM_CASES = [([5, 8, 11], "after"), ([5, 8], "after"), ([2, 7], "after"), ([5, 8, 11], "in"), ([3, 9], "in")]
+
+
+def unused_param_inputs():
+    """An 8 x 8 latent and a context for the dummy backward of ldm_diffusers.py:123-141 (the set of parameters without
+    gradient does not depend on the size)."""
+    g = torch.Generator().manual_seed(1)
+    return torch.rand((1, 4, 8, 8), generator=g), torch.rand((1, 77, 768), generator=g)
+
+
 def train_palette(K):
     return [int(v) for v in torch.randint(0, 256, (K * 3,), generator=torch.Generator().manual_seed(99))]
 

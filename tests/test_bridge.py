@@ -9,13 +9,21 @@
 * ``LdmRocm.exclude_unused_params`` freezes exactly the parameters the reference's dummy-backward procedure
   (ldm_diffusers.py:123-141) finds unused, for the shipped taps and for [5, 8] / 'in'-type taps.
 """
+import json
 import os
 
 import pytest
 import torch
 
-from oracle import sd_modules, ref_driver, madm_path
+from oracle import sd_modules, madm_path
 from madm_amd import weights
+
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def reference_names():
+    with open(os.path.join(GOLDEN_DIR, "reference_names.json")) as f:
+        return json.load(f)
 
 
 @pytest.fixture(scope="module")
@@ -85,23 +93,13 @@ def _product_model(device="cpu"):
                     vae_decoder_loss='st', vae_decoder_loss_type='L1')
 
 
-@pytest.mark.skipif(not ref_driver.available(), reason="needs /root/reference (build container)")
-def test_state_dict_keys_match_reference_classes(oracle_nets):
+def test_state_dict_keys_match_reference_classes():
     """Keys (and shapes) under backbone.* / sem_seg_head.* / ema_sem_seg_head.* of the product model vs a model assembled
     from the REFERENCE's BasePromptTimeGenerator / AttentionFeatureExtractorBackbone / DAFormerHead classes on the
-    diffusers-named oracle UNet / VAE -- what ODISECheckpointer matches by name when a released checkpoint is loaded."""
-    from copy import deepcopy
-    vae, unet = oracle_nets
-    ns = ref_driver.load_modeling()
-    backbone, head = madm_path.build_reference_eval_model(ns, vae, unet, madm_path.DEPTH_CFG)
-    ref = torch.nn.Module()
-    ref.backbone, ref.sem_seg_head = backbone, head
-    ref.sem_seg_head_sec_modal = head                      # cmdise.py:153-156: the same object under a second name
-    # CMDISE._inti_ema_weights (cmdise.py:307-335)
-    ref.backbone.ema_feature_projections = deepcopy(backbone.feature_projections)
-    ref.ema_sem_seg_head = deepcopy(head)
-    ref.backbone.feature_extractor.ema_clip_project_others = deepcopy(backbone.feature_extractor.clip_project_others)
-    want = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
+    diffusers-named oracle UNet / VAE -- what ODISECheckpointer matches by name when a released checkpoint is loaded.
+    The reference model's names and shapes are recorded in tests/golden/reference_names.json (gen_golden.py main_pins,
+    with the second head name and the EMA copies of CMDISE._inti_ema_weights, cmdise.py:153-156,307-335)."""
+    want = {k: tuple(v) for k, v in reference_names()["meta_arch_depth"].items()}
     got = {k: tuple(v.shape) for k, v in _product_model().state_dict().items()}
     skip = ("shared_noise", "uncond_inputs", "num_batches_tracked")
     for k, shp in want.items():
@@ -116,27 +114,14 @@ def test_state_dict_keys_match_reference_classes(oracle_nets):
     assert "backbone.feature_extractor.ldm_extractor.vae.encoder.mid_block.attentions.0.to_q.weight" in got
 
 
-@pytest.mark.skipif(not ref_driver.available(), reason="needs /root/reference (build container)")
 @pytest.mark.parametrize("taps,kind", [([5, 8, 11], "after"), ([5, 8], "after"), ([2, 7], "after"), ([5, 8, 11], "in"),
                                        ([3, 9], "in")])
-def test_exclude_unused_params_equals_reference_procedure(oracle_nets, taps, kind):
+def test_exclude_unused_params_equals_reference_procedure(taps, kind):
     """ldm_diffusers.py:123-141 on the CPU oracle (reference's own diffusion_unet, float32 instead of .cuda().half(), an
-    8 x 8 latent -- the set of parameters without gradient does not depend on the size) vs the structural rule."""
-    import torch.nn.functional as F
+    8 x 8 latent -- the set of parameters without gradient does not depend on the size) vs the structural rule.  The
+    reference procedure's result is recorded in tests/golden/reference_names.json (gen_golden.py main_pins)."""
     from madm_amd.ldm_rocm import LdmRocm
-    _, unet = oracle_nets
-    ref = ref_driver.load()
-    for p in unet.parameters():
-        p.requires_grad = True
-        p.grad = None
-    g = torch.Generator().manual_seed(1)
-    _, feats = ref.diffusion_unet(unet=unet, sample=torch.rand((1, 4, 8, 8), generator=g), timestep=torch.zeros(1).long(),
-                                  encoder_hidden_states=torch.rand((1, 77, 768), generator=g), res_time_embedding=None,
-                                  unet_block_indices=taps, unet_block_indices_type=kind)
-    F.mse_loss(input=feats[-1], target=torch.ones_like(feats[-1])).backward()
-    frozen_ref = {n for n, p in unet.named_parameters() if p.grad is None}
-    for p in unet.parameters():
-        p.grad = None
+    frozen_ref = set(reference_names()["unused_params"][f"{kind}:{','.join(map(str, taps))}"])
     m = LdmRocm("", [], taps, (), input_range='-1+1', unet_block_indices_type=kind, finetune_unet='all', weights='synthetic',
                 device='cpu')
     frozen = {n for n, p in m.unet.named_parameters() if not p.requires_grad}

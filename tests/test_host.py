@@ -256,22 +256,25 @@ def test_synthetic_parameters_are_name_keyed_and_deterministic(trees):
 
 def test_ldm_rocm_keeps_ldm_diffusers_class_surface():
     """Static attributes BasePromptTimeGenerator / FeatureExtractorBackbone read (ldm_base.py:769-774,940-960;
-    feature_extractor.py:89-113) -- compared with the reference class body when /root/reference exists."""
+    feature_extractor.py:89-113) -- compared with oracle/ldm_path.OracleLdm, the CPU restatement with the LdmDiffusers
+    surface on which the golden vectors of the reference's own classes were generated; the constructor keeps the
+    reference's argument order (OracleLdm's configuration arguments, after its four module arguments)."""
+    import inspect
     from madm_amd.ldm_rocm import LdmRocm
+    from oracle.ldm_path import OracleLdm
     assert LdmRocm.text_embed_shape == torch.Size([77, 768]) and LdmRocm.unet_time_embed_out_features == 1280
     assert LdmRocm.uncond_inputs_size == torch.Size([1, 77, 768]) and LdmRocm.latent_image_size == (64, 64)
-    ref = "/root/reference/modeling/meta_arch/ldm_diffusers.py"
-    if os.path.exists(ref):
-        src = open(ref).read()
-        for attr in ("feature_size", "feature_dims", "feature_strides", "num_groups", "grouped_indices", "timesteps",
-                     "input_mean", "input_std"):
-            m = re.search(rf"^\s+{attr}\s*=\s*(.+)$", src, flags=re.M)
-            assert m and eval(m.group(1)) == getattr(LdmRocm, attr), attr
-        import inspect
-        sig = list(inspect.signature(LdmRocm.__init__).parameters)
-        m = re.search(r"def __init__\(self, (.*?)\):", src, flags=re.S)
-        ref_args = [a.split("=")[0].strip() for a in m.group(1).replace("\n", " ").split(",")]
-        assert sig[1:1 + len(ref_args)] == ref_args
+    for attr in ("latent_image_size", "text_embed_shape", "unet_time_embed_out_features", "uncond_inputs_size",
+                 "feature_size", "feature_dims", "feature_strides", "num_groups", "grouped_indices", "input_mean",
+                 "input_std"):
+        want = getattr(OracleLdm, attr)
+        assert type(getattr(LdmRocm, attr)) is type(want) and getattr(LdmRocm, attr) == want, attr
+    assert LdmRocm.timesteps == 0                            # single-timestep extractor (the golden cases' default t)
+    sig = list(inspect.signature(LdmRocm.__init__).parameters)
+    oracle_args = list(inspect.signature(OracleLdm.__init__).parameters)[5:]      # after self, vae, unet, scheduler, uncond
+    assert sig[1] == "stable_diffusion_name_or_path" and sig[2:2 + 3] == oracle_args[:3]
+    pos = [sig.index(a) for a in oracle_args]              # every configuration argument, in the same order
+    assert pos == sorted(pos)
     with pytest.raises(NotImplementedError):
         LdmRocm("", [], [5, 8, 11], [], concat_pixel_shuffle=True, weights="synthetic", device="cpu")
 

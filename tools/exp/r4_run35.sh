@@ -7,8 +7,8 @@ cd $R
  python tools/exp/stamps_c3d.py 32 640 640 10 1 | head -2) 2>&1 | grep -v amdgpu.ids | tee $O/stamps_c3d.txt
 python -m pytest tests/test_ops_gpu.py tests/test_parity_gpu.py -q -m gpu -x > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest.log
 for i in 1 2; do
-  MADM_HIP_LIB=$R/build/libmadm_hip_full.so python bench.py --no-cpu-baseline --no-kernel-profile --no-alt-dtype > $O/bench_full_$i.json 2>/dev/null
-  python bench.py --no-cpu-baseline --no-kernel-profile --no-alt-dtype > $O/bench_row_$i.json 2>/dev/null
+  MADM_HIP_LIB=$R/build/libmadm_hip_full.so python bench.py --full --no-cpu-baseline --no-kernel-profile --no-alt-dtype > $O/bench_full_$i.json 2>/dev/null
+  python bench.py --full --no-cpu-baseline --no-kernel-profile --no-alt-dtype > $O/bench_row_$i.json 2>/dev/null
 done
 python - <<'PY'
 import json,glob

@@ -5,6 +5,6 @@ cd $R
 timeout 1500 python tools/tune_concurrent.py --only "k3 " --min-us 25 --rows $O/tuned_side.txt > $O/tune.txt 2>&1; echo "tune rc=$?"; cat $O/tuned_side.txt
 B="--no-cpu-baseline --no-kernel-profile --no-alt-dtype"
 for i in 1 2; do
-  python bench.py $B 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('table  ', d['value'], d['ms_per_step'], d['serial_ms_per_step'])"
-  MADM_TUNED_FILE=$O/tuned_side.txt python bench.py $B 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('new rows', d['value'], d['ms_per_step'], d['serial_ms_per_step'])"
+  python bench.py --full $B 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('table  ', d['value'], d['ms_per_step'], d['serial_ms_per_step'])"
+  MADM_TUNED_FILE=$O/tuned_side.txt python bench.py --full $B 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('new rows', d['value'], d['ms_per_step'], d['serial_ms_per_step'])"
 done

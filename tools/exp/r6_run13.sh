@@ -16,7 +16,7 @@ import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1', d['value'], d['unit'], d['ms_per_step'], 'ms/step; serial', d.get('serial_ms_per_step'))"; }
 for i in 1 2; do
-python bench.py --no-cpu-baseline --no-alt-dtype --no-kernel-profile 2>/dev/null | show "default                       "
-MADM_HIP_LIB=$R/build/libmadm_hip_h16respf.so python bench.py --no-cpu-baseline --no-alt-dtype --no-kernel-profile 2>/dev/null | show "residual L2 prefetch          "
-MADM_TUNED_FILE=$R/tools/exp/r6_side_rows_w0.txt python bench.py --no-cpu-baseline --no-alt-dtype --no-kernel-profile 2>/dev/null | show "side-by-side rows at weight 0 "
+python bench.py --full --no-cpu-baseline --no-alt-dtype --no-kernel-profile 2>/dev/null | show "default                       "
+MADM_HIP_LIB=$R/build/libmadm_hip_h16respf.so python bench.py --full --no-cpu-baseline --no-alt-dtype --no-kernel-profile 2>/dev/null | show "residual L2 prefetch          "
+MADM_TUNED_FILE=$R/tools/exp/r6_side_rows_w0.txt python bench.py --full --no-cpu-baseline --no-alt-dtype --no-kernel-profile 2>/dev/null | show "side-by-side rows at weight 0 "
 done | tee $O/bench_ab.txt

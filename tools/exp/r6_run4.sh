@@ -15,7 +15,7 @@ export MADM_HIP_LIB=$R/build/libmadm_hip_h16stamps.so
 unset MADM_HIP_LIB
 for pr in 0 1 2; do
   echo "== bench, tap prio $pr"
-  MADM_H16_TAP_PRIO=$pr python bench.py --no-cpu-baseline --no-alt-dtype 2>/dev/null | python -c "
+  MADM_H16_TAP_PRIO=$pr python bench.py --full --no-cpu-baseline --no-alt-dtype 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('value', d['value'], 'serial', d.get('serial_ms_per_step'), 'roofline', d['roofline']['achieved'], d['roofline']['frac'])"

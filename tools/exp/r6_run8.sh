@@ -9,10 +9,10 @@ import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1', d['value'], 'images/s', d['ms_per_step'], 'ms/step; serial', d.get('serial_ms_per_step'))"; }
 for wl in eval slide; do
-  python bench.py --workload $wl --steps 40 --warmup 8 --no-kernel-profile 2>$O/err_$wl.txt | show "$wl graphed 4 streams"
+  python bench.py --full --workload $wl --steps 40 --warmup 8 --no-kernel-profile 2>$O/err_$wl.txt | show "$wl graphed 4 streams"
   for cfg in "2 6" "2 8" "1 4" "2 4"; do
     set -- $cfg
-    python bench.py --workload $wl --steps 40 --warmup 8 --no-kernel-profile --eval-runner staged --pipeline $1 --slots $2 2>>$O/err_$wl.txt | show "$wl staged unet_streams $1 slots $2"
+    python bench.py --full --workload $wl --steps 40 --warmup 8 --no-kernel-profile --eval-runner staged --pipeline $1 --slots $2 2>>$O/err_$wl.txt | show "$wl staged unet_streams $1 slots $2"
   done
 done | tee $O/eval_ab.txt
 tail -5 $O/err_eval.txt

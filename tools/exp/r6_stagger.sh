@@ -15,7 +15,7 @@ for shape in "512 512 128 128 --gn" "512 512 128 128" "512 512 128 128 --gn --re
 done | tee $O/layers.txt
 for st in 0 5000 9000; do
   echo "== bench, stagger $st"
-  MADM_H16_STAGGER=$st python bench.py --no-cpu-baseline --no-alt-dtype 2>/dev/null | python -c "
+  MADM_H16_STAGGER=$st python bench.py --full --no-cpu-baseline --no-alt-dtype 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('value', d['value'], 'serial', d.get('serial_ms_per_step'), 'roofline', d['roofline']['achieved'], d['roofline']['frac'])"

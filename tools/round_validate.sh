@@ -6,10 +6,10 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$tag; mkdir -p $O
 cd $R
 bash tools/first_touch.sh; python -m pytest tests -m gpu -q > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee $O/rc.txt; tail -3 $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" | tee -a $O/rc.txt; tail -2 $O/smoke.log
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/rc.txt; cut -c1-900 $O/bench.json
-python bench.py --dtype bf16 --no-cpu-baseline > $O/bench_bf16.json 2> /dev/null; cut -c1-200 $O/bench_bf16.json
-python bench.py --workload eval --steps 10 --warmup 2 > $O/bench_eval.json 2> $O/bench_eval.err; cut -c1-300 $O/bench_eval.json
-python bench.py --workload slide --steps 5 --warmup 2 > $O/bench_slide.json 2> $O/bench_slide.err; cut -c1-300 $O/bench_slide.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/rc.txt; cut -c1-900 $O/bench.json
+python bench.py --full --dtype bf16 --no-cpu-baseline > $O/bench_bf16.json 2> /dev/null; cut -c1-200 $O/bench_bf16.json
+python bench.py --full --workload eval --steps 10 --warmup 2 > $O/bench_eval.json 2> $O/bench_eval.err; cut -c1-300 $O/bench_eval.json
+python bench.py --full --workload slide --steps 5 --warmup 2 > $O/bench_slide.json 2> $O/bench_slide.err; cut -c1-300 $O/bench_slide.json
 python bench.py --workload train --steps 5 --warmup 2 > $O/bench_train.json 2> $O/bench_train.err; cut -c1-300 $O/bench_train.json
 python tools/precision_report.py > $O/precision.txt 2>&1; tail -3 $O/precision.txt
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 tools/ddp_check.py > $O/ddp_check_raw.txt 2>&1; grep -v "^\[W\|Gloo\|amdgpu.ids" $O/ddp_check_raw.txt > $O/ddp_check.txt; tail -2 $O/ddp_check.txt
