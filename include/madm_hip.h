@@ -565,6 +565,18 @@ int madm_gray_sum(const float* img, size_t HW, double* out, void* stream);
 int madm_color_jitter_step(const float* in, float* out, size_t HW, int op, float factor, const double* gray_sum, void* stream);
 int madm_blur_axis_f32(const float* in, float* out, int planes, int H, int W, int axis, int ksize, const float* weights,
                        void* stream);
+/* masked image consistency (BlockMaskGenerator.mask_image, utils/dacs_transforms.py:136-166) on an f32 NCHW batch
+ * [B][C][H][W] with a keep-probability grid keep_u f32 [B][gh][gw] (torch.rand of the host):
+ * madm_mic_minmax writes madm_mic_minmax_parts(n) (min, max) pairs of x[0..n) into parts (f32 [nparts][2]; a block that
+ * saw a NaN writes (NaN, NaN)); madm_block_mask folds them into the batch's (min, max) ON THE DEVICE and writes
+ * out = in with every pixel whose grid cell has keep_u <= mask_ratio replaced -- cell (min(floor(y scale_y), gh - 1),
+ * min(floor(x scale_x), gw - 1)), scale = (float)gh / H as upsample_nearest2d computes it -- by 0.5 when the batch lies
+ * in [0, 1], by x * 0 when it lies in [-1, 1], else by 127.5; outside [0, 255] (or NaN) it also sets *flag = 1 (the
+ * reference's assert, raised by the host after the step).  in == out allowed. */
+int madm_mic_minmax_parts(size_t n);
+int madm_mic_minmax(const float* x, size_t n, float* parts, int nparts, void* stream);
+int madm_block_mask(const float* in, float* out, int B, int C, int H, int W, const float* keep_u, int gh, int gw,
+                    float scale_y, float scale_x, float mask_ratio, const float* parts, int nparts, int* flag, void* stream);
 /* backward of madm_tanh_gate for dout [repeat][n]: with g_i = sum_r dout[r][i], dx1 += tanh(a1) g, da1 += (1 - tanh^2(a1))
  * x1 g and likewise for (a2, x2); every output is ACCUMULATED into and may be NULL. */
 int madm_tanh_gate_bwd(const float* a1, const float* x1, const float* a2, const float* x2, const float* dout, float* da1,

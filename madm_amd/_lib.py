@@ -202,6 +202,10 @@ SYMBOLS = [
     ("madm_gray_sum", c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
     ("madm_color_jitter_step", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_void_p, c_void_p]),
     ("madm_blur_axis_f32", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("madm_mic_minmax_parts", c_int, [c_size_t]),
+    ("madm_mic_minmax", c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    ("madm_block_mask", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float,
+                                c_float, c_void_p, c_int, c_void_p, c_void_p]),
     ("madm_tanh_gate_bwd", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_size_t, c_int, c_void_p]),
 ]

@@ -103,3 +103,48 @@ def strong_color(param, data, generator=None, rng=np.random):
         sigma = rng.uniform(0.15, 1.15)
         data = gaussian_blur(data, sigma)
     return data
+
+
+def mask_grid_shape(H, W, mask_block_size=32):
+    """(gh, gw) of BlockMaskGenerator.generate_mask: Python's round (banker's rounding: round(2.5) == 2)."""
+    return round(H / mask_block_size), round(W / mask_block_size)
+
+
+def block_mask(imgs, mask_ratio, mask_block_size=32, generator=None, keep_u=None):
+    """``BlockMaskGenerator(mask_ratio, mask_block_size).mask_image(imgs)`` (dacs_transforms.py:136-166) on f32 NCHW
+    ``imgs`` [B, C, H, W]: one keep grid per image, broadcast over the channels.  The grid u ~ U(0, 1) [B, 1, gh, gw] is
+    drawn from torch's CPU generator (``generator``, default: the global one) and uploaded without a sync; ``keep_u``
+    injects it instead.  The fill (0.5 / x * 0 / 127.5) is chosen on the device from the batch's range.
+    Returns (masked copy, device grid [B, 1, gh, gw], device int32 flag: 1 when the batch lies outside [0, 255], where
+    the reference asserts -- the caller raises on it at its next host sync, ``check_mask_flag``)."""
+    ops._need_cuda(imgs)
+    assert imgs.dim() == 4 and imgs.dtype == torch.float32
+    B, C, H, W = imgs.shape
+    gh, gw = mask_grid_shape(H, W, mask_block_size)
+    if gh < 1 or gw < 1:
+        raise ValueError(f"block_mask: a {H} x {W} image has no {mask_block_size}-pixel mask block")
+    imgs = imgs.contiguous()
+    dev = imgs.device
+    if keep_u is None:
+        keep_u = torch.rand((B, 1, gh, gw), generator=generator)
+        keep_u = keep_u.pin_memory().to(dev, non_blocking=True)
+    else:
+        assert tuple(keep_u.shape) == (B, 1, gh, gw)
+        keep_u = keep_u.to(device=dev, dtype=torch.float32).contiguous()
+    n = imgs.numel()
+    nparts = lib.madm_mic_minmax_parts(n)
+    parts = torch.empty((nparts, 2), dtype=torch.float32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.empty_like(imgs)
+    ops.check(lib.madm_mic_minmax(imgs.data_ptr(), n, parts.data_ptr(), nparts, _s()), "madm_mic_minmax")
+    # upsample_nearest2d's source index: floor(dst * (float)in / out), the scale rounded to f32 as PyTorch computes it
+    sy, sx = float(np.float32(gh) / np.float32(H)), float(np.float32(gw) / np.float32(W))
+    ops.check(lib.madm_block_mask(imgs.data_ptr(), out.data_ptr(), B, C, H, W, keep_u.data_ptr(), gh, gw, sy, sx,
+                                  float(mask_ratio), parts.data_ptr(), nparts, flag.data_ptr(), _s()), "madm_block_mask")
+    return out, keep_u, flag
+
+
+def check_mask_flag(flag):
+    """The reference's ``assert 0 <= min <= max <= 255`` of mask_image, read back (one host sync)."""
+    if int(flag.item()) != 0:
+        raise AssertionError("BlockMaskGenerator.mask_image (dacs_transforms.py:163): the image batch lies outside [0, 255]")

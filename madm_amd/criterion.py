@@ -49,14 +49,28 @@ class CmdiseCriterion(torch.nn.Module):
     @staticmethod
     def decoder_loss_forward(pred, gt, mask, loss_weight, loss_type):
         """pred / gt: f32 [B, 4, h, w]; mask: f32 [B, 1, H, W].  Returns (loss scalar, ctx)."""
-        pred, gt, mask = pred.float().contiguous(), gt.float().contiguous(), mask.float().contiguous()
+        pred, gt = pred.float().contiguous(), gt.float().contiguous()
+        mask = None if mask is None else mask.float().contiguous()
         s = torch.zeros(1, dtype=torch.float64, device=pred.device)
         ops.masked_l1(pred, gt, mask, l2=(loss_type != 'L1'), loss_sum=s)
         coef = float(loss_weight) / pred.numel()
         return (s * coef).to(torch.float32).reshape(()), dict(pred=pred, gt=gt, mask=mask, l2=(loss_type != 'L1'), coef=coef)
 
     @staticmethod
+    def mic_decoder_loss_forward(pred, gt, pixel_weight, loss_weight, loss_type):
+        """mic_vae_decoder_loss (:247-253): ``l1_loss(pred, gt) * pixel_weight * loss_weight`` (mse_loss unless 'L1'), the
+        mean over every element; pixel_weight: f32 device scalar [1] (pseudo_val, no host sync) or None (1.0)."""
+        loss, ctx = CmdiseCriterion.decoder_loss_forward(pred, gt, None, loss_weight, loss_type)
+        if pixel_weight is not None:
+            pw = pixel_weight.float().reshape(1)
+            loss = (loss * pw).reshape(())
+            ctx["pw"] = pw
+        return loss, ctx
+
+    @staticmethod
     def decoder_loss_backward(ctx, g):
+        if ctx.get("pw") is not None:        # a device pixel weight (mic_decoder_loss_forward) rides on the upstream scalar
+            g = g.reshape(1).float() * ctx["pw"]
         _, d = ops.masked_l1(ctx["pred"], ctx["gt"], ctx["mask"], l2=ctx["l2"], gscale=g.reshape(1).float().contiguous(),
                              coef=ctx["coef"], want_grad=True)
         return d

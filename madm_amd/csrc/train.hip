@@ -464,6 +464,128 @@ __global__ __launch_bounds__(256) void blur_axis_kernel(const float* __restrict_
     }
 }
 
+// ---- masked image consistency (BlockMaskGenerator.mask_image, utils/dacs_transforms.py:136-166) ----
+// Pass 1: per-block (min, max) of a flat f32 batch into part[blockIdx.x] (plain stores, no atomics and no initialisation:
+// the mask kernel folds the few partials).  A NaN anywhere makes its block's pair (NaN, NaN): the reference's range tests
+// are all false for a NaN minimum, so it lands in the out-of-range case.
+constexpr int MIC_MAX_PARTS = 256;
+__global__ __launch_bounds__(256) void mic_minmax_kernel(const float* __restrict__ x, size_t n, float2* __restrict__ part) {
+    __shared__ float s_lo[4], s_hi[4];
+    __shared__ int s_nan[4];
+    float lo = INFINITY, hi = -INFINITY;
+    bool nan = false;
+    const size_t n4 = n / 4, stride = (size_t)gridDim.x * blockDim.x;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {          // four 16-byte loads in flight per thread
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = reinterpret_cast<const float4*>(x)[i + u * stride];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            nan |= (v[u].x != v[u].x) | (v[u].y != v[u].y) | (v[u].z != v[u].z) | (v[u].w != v[u].w);
+            lo = fminf(fminf(lo, v[u].x), fminf(fminf(v[u].y, v[u].z), v[u].w));
+            hi = fmaxf(fmaxf(hi, v[u].x), fmaxf(fmaxf(v[u].y, v[u].z), v[u].w));
+        }
+    }
+    for (; i < n4; i += stride) {
+        const float4 v = reinterpret_cast<const float4*>(x)[i];
+        nan |= (v.x != v.x) | (v.y != v.y) | (v.z != v.z) | (v.w != v.w);
+        lo = fminf(fminf(lo, v.x), fminf(fminf(v.y, v.z), v.w));
+        hi = fmaxf(fmaxf(hi, v.x), fmaxf(fmaxf(v.y, v.z), v.w));
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const float a = x[n4 * 4 + threadIdx.x];
+        nan |= (a != a);
+        lo = fminf(lo, a);
+        hi = fmaxf(hi, a);
+    }
+    int bad = nan ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, o));
+        hi = fmaxf(hi, __shfl_xor(hi, o));
+        bad |= __shfl_xor(bad, o);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_lo[w] = lo; s_hi[w] = hi; s_nan[w] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < (int)(blockDim.x >> 6); ++k) { lo = fminf(lo, s_lo[k]); hi = fmaxf(hi, s_hi[k]); bad |= s_nan[k]; }
+        part[blockIdx.x] = bad ? make_float2(NAN, NAN) : make_float2(lo, hi);
+    }
+}
+
+// Pass 2: out = imgs with the masked 32 x 32 blocks filled.  keep(b, y, x) = u[b][gy][gx] > ratio with PyTorch's nearest
+// index gy = min(floor(y * sy), gh - 1), sy = (float)gh / H (upsample_nearest2d, scales = None).  The fill is chosen on the
+// device from the batch's (min, max) -- the fold of the nparts pairs of pass 1 -- in the reference's order:
+//   0 <= min <= max <= 1  -> masked pixels = 0.5;   -1 <= min <= max <= 1 -> x * keep;   0 <= min <= max <= 255 -> 127.5;
+//   anything else (the reference asserts) -> *flag = 1 for the host to raise on, pixels as in the 127.5 case.
+// VEC consecutive pixels of one row per thread (16-byte loads / stores when W % 4 == 0).  in == out is allowed.
+template <int VEC>
+__global__ __launch_bounds__(256) void block_mask_kernel(const float* in, float* out, int B, int C, int H, int W,
+                                                         const float* __restrict__ u, int gh, int gw, float sy, float sx,
+                                                         float ratio, const float2* __restrict__ part, int nparts,
+                                                         int* __restrict__ flag) {
+    __shared__ float s_lo[4], s_hi[4];
+    __shared__ int s_nan[4];
+    float lo = INFINITY, hi = -INFINITY;
+    int bad = 0;
+    for (int k = threadIdx.x; k < nparts; k += blockDim.x) {
+        const float2 p = part[k];
+        bad |= (p.x != p.x) ? 1 : 0;
+        lo = fminf(lo, p.x);
+        hi = fmaxf(hi, p.y);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, o));
+        hi = fmaxf(hi, __shfl_xor(hi, o));
+        bad |= __shfl_xor(bad, o);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_lo[w] = lo; s_hi[w] = hi; s_nan[w] = bad; }
+    __syncthreads();
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) { lo = fminf(lo, s_lo[k]); hi = fmaxf(hi, s_hi[k]); bad |= s_nan[k]; }
+    int mode = 3;
+    if (!bad) {
+        if (0.f <= lo && lo <= hi && hi <= 1.f) mode = 0;
+        else if (-1.f <= lo && lo <= hi && hi <= 1.f) mode = 1;
+        else if (0.f <= lo && lo <= hi && hi <= 255.f) mode = 2;
+    }
+    if (mode == 3 && blockIdx.x == 0 && threadIdx.x == 0) *flag = 1;
+    const float fill = mode == 0 ? 0.5f : 127.5f;
+    const int WV = W / VEC;
+    const size_t total = (size_t)B * C * H * WV;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int xv = (int)(i % WV);
+        const size_t r = i / WV;                    // row index over (b, c, y)
+        const int y = (int)(r % H);
+        const int b = (int)(r / ((size_t)H * C));
+        const int gy = min((int)floorf((float)y * sy), gh - 1);
+        const float* urow = u + ((size_t)b * gh + gy) * gw;
+        float v[VEC];
+        if constexpr (VEC == 4) {
+            const float4 t = reinterpret_cast<const float4*>(in)[i];
+            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+        } else {
+            v[0] = in[i];
+        }
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            const int x = xv * VEC + j;
+            const int gx = min((int)floorf((float)x * sx), gw - 1);
+            const bool keep = urow[gx] > ratio;
+            if (mode == 1) v[j] = v[j] * (keep ? 1.f : 0.f);
+            else if (!keep) v[j] = fill;
+        }
+        if constexpr (VEC == 4) {
+            reinterpret_cast<float4*>(out)[i] = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+            out[i] = v[0];
+        }
+    }
+}
+
 unsigned grid_for(size_t n, unsigned cap = 8192) {
     size_t g = (n + 255) / 256;
     if (g > cap) g = cap;
@@ -613,6 +735,44 @@ int madm_tanh_gate_bwd(const float* a1, const float* x1, const float* a2, const 
     MADM_REQUIRE(x1 && dout && n > 0 && repeat > 0 && (!a2 || x2), "tanh_gate_bwd: bad argument");
     tanh_gate_bwd_kernel<<<grid_for(n), 256, 0, (hipStream_t)stream>>>(a1, x1, a2, x2, dout, da1, dx1, da2, dx2, n, repeat);
     return madm_check_launch("tanh_gate_bwd_kernel");
+}
+
+int madm_mic_minmax_parts(size_t n) {
+    if (n == 0) return 0;
+    size_t g = (n / 4 + 1023) / 1024;      // >= 4 float4 per thread
+    if (g < 1) g = 1;
+    if (g > MIC_MAX_PARTS) g = MIC_MAX_PARTS;
+    return (int)g;
+}
+
+int madm_mic_minmax(const float* x, size_t n, float* parts, int nparts, void* stream) {
+    MADM_REQUIRE(x && parts && n > 0 && nparts == madm_mic_minmax_parts(n), "mic_minmax: bad argument");
+    MADM_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)parts & 7) == 0, "mic_minmax: misaligned pointer");
+    mic_minmax_kernel<<<(unsigned)nparts, 256, 0, (hipStream_t)stream>>>(x, n, reinterpret_cast<float2*>(parts));
+    return madm_check_launch("mic_minmax_kernel");
+}
+
+int madm_block_mask(const float* in, float* out, int B, int C, int H, int W, const float* keep_u, int gh, int gw,
+                    float scale_y, float scale_x, float mask_ratio, const float* parts, int nparts, int* flag, void* stream) {
+    MADM_REQUIRE(in && out && keep_u && parts && flag && B > 0 && C > 0 && H > 0 && W > 0 && gh > 0 && gw > 0 &&
+                     nparts > 0 && nparts <= MIC_MAX_PARTS,
+                 "block_mask: bad argument");
+    MADM_REQUIRE((in == out) || (out + (size_t)B * C * H * W <= in) || (in + (size_t)B * C * H * W <= out),
+                 "block_mask: in and out overlap partially");
+    // the index math of the kernel must reproduce floor(dst * scale) < src size for every dst (a bad scale would read
+    // past the grid row): the clamp to gh - 1 / gw - 1 holds that, whatever the caller passes
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = W % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0;
+    const size_t total = (size_t)B * C * H * W / (vec ? 4 : 1);
+    if (vec)
+        block_mask_kernel<4><<<grid_for(total, 4096), 256, 0, s>>>(in, out, B, C, H, W, keep_u, gh, gw, scale_y, scale_x,
+                                                                   mask_ratio, reinterpret_cast<const float2*>(parts), nparts,
+                                                                   flag);
+    else
+        block_mask_kernel<1><<<grid_for(total, 4096), 256, 0, s>>>(in, out, B, C, H, W, keep_u, gh, gw, scale_y, scale_x,
+                                                                   mask_ratio, reinterpret_cast<const float2*>(parts), nparts,
+                                                                   flag);
+    return madm_check_launch("block_mask_kernel");
 }
 
 }  // extern "C"

@@ -14,11 +14,18 @@ passes are recorded (block-boundary tape of the UNet, raw conv outputs of projec
 the outputs of ONE autograd node (``_TrainStepFn``) whose backward walks those records with the explicit gradient kernels
 (backward.py, head.py, backbone.py, criterion.py), weighting each loss by the upstream gradient it receives.
 
-Options of the reference that no shipped config enables (mic / mic_reg, mask_diff, noise_reg, denoise_supervise, fd,
-fd_attention, merge_with_pl_data, remove_amp / remove_texture, sem_seg_head_sec_modal=True, prompt masking) raise
-NotImplementedError.  ``reg_uncertain`` only feeds the reference's visualisation (:323-328 -> vis_data :556-560); it is
-accepted and changes nothing but the teacher call's ``return_unet_final_output`` (which the VAE-decoder branch computes
-anyway).  The periodic matplotlib dump (``vis_results``) is out of scope.
+Masked image consistency (``mic`` / ``mic_reg``, :404-420, :471-488; MIC, Hoyer et al. 2023): a third recorded student
+pass on the colour-augmented target image with 32 x 32 blocks masked (augment.block_mask), under the target adapter; ``mic``
+adds ``masked_prompt_consistency_loss`` (CE of its logits against the teacher's pseudo labels), ``mic_reg`` skips the
+projections and the head and adds ``mic_vae_decoder_loss`` (L1 / L2 of its UNet output against the colour latent of the
+pseudo labels).  The reference runs it at one image per process only (it raises for B > 1); here every image gets its own
+mask and its own pseudo labels in the masked CE -- the same values at B = 1 (masked image consistency).
+
+Options of the reference that no shipped config enables (mask_diff, noise_reg, denoise_supervise, fd, fd_attention,
+merge_with_pl_data, remove_amp / remove_texture, sem_seg_head_sec_modal=True, prompt masking) raise NotImplementedError.
+``reg_uncertain`` only feeds the reference's visualisation (:323-328 -> vis_data :556-560); it is accepted and changes nothing
+but the teacher call's ``return_unet_final_output`` (which the VAE-decoder branch computes anyway).  The periodic matplotlib
+dump (``vis_results``) is out of scope.
 """
 import os
 import random
@@ -28,7 +35,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops, labels as L, optim
+from . import augment, ops, labels as L, optim
 from . import backward as bw
 from .meta_arch import MadmInference
 from .nn import Tok
@@ -44,14 +51,15 @@ class MTMADISE(MadmInference):
                  sem_seg_head_sec_modal=False, ema_alpha=0.999, pseudo_threshold=0.968, blur=True, color_jitter_strength=0.2,
                  color_jitter_probability=0.2, enable_mixup=True, pl_crop=False, color_aug_flag=True, ema_w_unet=False,
                  pixel_mean=(0.0, 0.0, 0.0), pixel_std=(255.0, 255.0, 255.0), size_divisibility=64, color_aug=None,
-                 **unsupported):
+                 mic=False, mask_ratio=None, mic_reg=False, MIC_reg_wo_pl_val=False, **unsupported):
         for k, v in unsupported.items():
-            if k in ("mic", "mic_reg", "mask_diff", "noise_reg", "denoise_supervise", "fd", "fd_attention",
-                     "merge_with_pl_data", "remove_amp", "remove_texture", "prompt_confidence", "MIC_reg_wo_pl_val",
+            if k in ("mask_diff", "noise_reg", "denoise_supervise", "fd", "fd_attention",
+                     "merge_with_pl_data", "remove_amp", "remove_texture", "prompt_confidence",
                      "w_rgb_lora", "wo_lora") and v:
                 raise NotImplementedError(f"MTMADISE option {k}={v!r}: no shipped config enables it (SURVEY.md App. C.11)")
         if sem_seg_head_sec_modal:
             raise NotImplementedError("sem_seg_head_sec_modal=True (a second head copy) is not built")
+        assert not (mic and mic_reg), "mic and mic_reg exclude each other (mtmadise.py:78-81)"
         super().__init__(backbone, sem_seg_head, target_modality=target_modality, lora_configs=lora_configs,
                          pixel_mean=pixel_mean, pixel_std=pixel_std, size_divisibility=size_divisibility,
                          eval_with_noise=eval_with_noise)
@@ -77,6 +85,11 @@ class MTMADISE(MadmInference):
         self.denoise_timestep_range = denoise_timestep_range
         self.train_max_iter = max_iter
         self.ema_w_unet = ema_w_unet
+        # masked image consistency (cmdise.py:136-137,181-184; mtmadise.py:36,41,78-81): BlockMaskGenerator(ratio, 32)
+        self.mic, self.mic_reg, self.MIC_reg_wo_pl_val = bool(mic), mic_reg, MIC_reg_wo_pl_val
+        self.mask_ratio = 0.7 if mask_ratio is None else mask_ratio
+        self.mask_block_size = 32
+        self.deferred_mask_flags = None     # a list: the trainer collects the range flags of mask_image and raises at its end
         self.train_palette = L.pad_palette(train_palette)                       # mtmadise.py:97-99
         if reg_target_palette is None:
             self.reg_target_palette = list(self.train_palette)
@@ -142,10 +155,12 @@ class MTMADISE(MadmInference):
         assert H % d == 0 and W % d == 0, "label padding (ImageList pads labels with 0) is not needed by the shipped 512 crops"
         return g.contiguous()
 
-    def _student_pass(self, img, input_modal):
+    def _student_pass(self, img, input_modal, head=True):
         """backbone(img, return_unet_final_output=True, input_modal=...) + sem_seg_head, recorded for the backward:
         feature_extractor.py:156-170 -> ldm_base.py:832-924 -> ldm_diffusers.py:143-217 -> feature_extractor.py:367-396 ->
-        daformer_head.py:702-749.  Returns (logit tokens Tok, unet_final_output dict, record)."""
+        daformer_head.py:702-749.
+        Returns (logit tokens Tok, unet_final_output dict, record); ``head=False`` (the mic_reg pass): encoder and UNet only,
+        no projections / head, logits None."""
         bb = self.backbone
         gen = bb.feature_extractor
         ldm = gen.ldm_extractor
@@ -160,12 +175,14 @@ class MTMADISE(MadmInference):
                                            return_unet_final_output=True)
             keep = ldm._grad_keep
             ldm._grad_keep = None
-            proj_tape = []
-            fd = bb.forward_features_recorded(feats, img.shape[-2:], proj_tape)
-            head = self.sem_seg_head
-            head_tape = {}
-            toks = [fd['output_features'].tok[k] for k in head.in_keys]
-            logits = head.forward_tokens(toks, tape=head_tape)
+            proj_tape, head_tape, logits = None, None, None
+            if head:
+                proj_tape = []
+                fd = bb.forward_features_recorded(feats, img.shape[-2:], proj_tape)
+                hd = self.sem_seg_head
+                head_tape = {}
+                toks = [fd['output_features'].tok[k] for k in hd.in_keys]
+                logits = hd.forward_tokens(toks, tape=head_tape)
         no_grad_w = ()
         if ldm.vae_decoder_loss and not ldm.final_fuse_vae_decoder_feat:
             no_grad_w = (feats[0].W,)          # the decoder image is ``.detach()``ed (ldm_diffusers.py:196-201)
@@ -180,12 +197,12 @@ class MTMADISE(MadmInference):
         lat = vae_encoder(vae=self.backbone.feature_extractor.ldm_extractor.vae, images=rgb, encoder_block_indices=[])[0]
         return lat, valid
 
-    def _strong_color(self, strong_parameters, data):
-        if not self.color_aug_flag:
+    def _strong_color(self, strong_parameters, data, force=False):
+        """``force``: the masked image's strong_transform call passes no color_aug_flag (mtmadise.py:406): always on."""
+        if not (self.color_aug_flag or force):
             return data
         if self.color_aug is not None:
             return self.color_aug(strong_parameters, data)
-        from . import augment
         return augment.strong_color(strong_parameters, data)
 
     # ------------------------------------------------------------------ forward
@@ -281,12 +298,25 @@ class MTMADISE(MadmInference):
         self.set_lora_adapter(state=tmod)
         target_logits, target_out, rec_t = self._student_pass(mixed_img, 'mixed')
 
+        # ---- masked image consistency: the masked pass (:404-420) -- reads nothing of the teacher, so it runs before the wait ----
+        rec_m = masked_img = mask_u = mask_flag = None
+        if self.mic or self.mic_reg:
+            with torch.no_grad():
+                strong_parameters['mix'] = None
+                masked_img = self._strong_color(strong_parameters, target.clone(), force=True)   # torch jitter, numpy sigma
+                masked_img, mask_u, mask_flag = augment.block_mask(masked_img, self.mask_ratio,
+                                                                   self.mask_block_size)     # then the torch grid
+            self.set_lora_adapter(state=tmod)
+            masked_logits, masked_out, rec_m = self._student_pass(masked_img, 'others', head=bool(self.mic))
+
         # ---- label / weight mixing with the teacher's pseudo labels ----
         if overlap:
             main_stream.wait_stream(side)
             for t_side in (ema_nchw, pseudo_prob, pseudo_label, pseudo_weight):
                 t_side.record_stream(main_stream)
         with torch.no_grad():
+            # pseudo_val (:347-348) as a device scalar, taken before pl_crop zeroes the top rows of the weight
+            pseudo_val = pseudo_weight.reshape(-1)[:1].clone() if self.mic_reg else None
             if self.pl_crop:
                 pseudo_weight[:, :self.psweight_ignore_top, :] = 0
             if self.enable_mixup:
@@ -305,6 +335,8 @@ class MTMADISE(MadmInference):
             if 't' in self.vae_decoder_loss:
                 target_color_gt_latent, target_color_gt_mask = self._color_latent(mixed_lbl, self.reg_target_palette)
                 target_color_gt_mask = target_color_gt_mask * pseudo_weight[:, None]
+            if self.mic_reg:                                                              # :343-345
+                pl_color_latent, _ = self._color_latent(pseudo_label[:, None], self.reg_target_palette)
 
             # ---- losses (criterion.py:155-254) ----
             losses = {}
@@ -319,6 +351,18 @@ class MTMADISE(MadmInference):
                 losses['vae_decoder_target_loss'], ctxs['vae_decoder_target_loss'] = crit.decoder_loss_forward(
                     target_out['before_vae.decoder'], target_color_gt_latent, target_color_gt_mask,
                     self.vae_decoder_loss_weight[1], self.vae_decoder_loss_type)
+            if self.mic:            # :471-476 -> criterion.py:211-218; per-image pseudo labels for B > 1
+                losses['masked_prompt_consistency_loss'], ctxs['masked_prompt_consistency_loss'] = crit.ce_forward(
+                    masked_logits, K, pseudo_label, pixel_weight=pseudo_weight)
+            if self.mic_reg:        # :477-488 -> criterion.py:247-253
+                pw = None if self.MIC_reg_wo_pl_val else pseudo_val
+                losses['mic_vae_decoder_loss'], ctxs['mic_vae_decoder_loss'] = crit.mic_decoder_loss_forward(
+                    masked_out['before_vae.decoder'], pl_color_latent, pw, self.mic_reg, self.vae_decoder_loss_type)
+        if mask_flag is not None:   # mask_image's range assert: at the trainer's end-of-step sync, else here (one sync)
+            if self.deferred_mask_flags is not None:
+                self.deferred_mask_flags.append(mask_flag)
+            else:
+                augment.check_mask_flag(mask_flag)
         self.train_iter_index += 1
 
         names = list(losses.keys())
@@ -328,10 +372,15 @@ class MTMADISE(MadmInference):
             losses['zero_grad'] = torch.zeros((), device=source.device)     # value 0, gradient 0 (not None) for each of them
             names.append('zero_grad')
             zero_ids = {id(p) for p in self.unused_lora_parameters(tmod) if p.requires_grad}
-        state = dict(model=self, names=names, ctxs=ctxs, rec_s=rec_s, rec_t=rec_t, params=params, zero_ids=zero_ids)
+        state = dict(model=self, names=names, ctxs=ctxs, rec_s=rec_s, rec_t=rec_t, rec_m=rec_m, params=params,
+                     zero_ids=zero_ids)
         self.last_step = dict(mixed_img=mixed_img, mixed_lbl=mixed_lbl, mixed_seg_weight=mixed_seg_weight,
                               pseudo_label=pseudo_label, pseudo_weight=pseudo_weight, ema_logits=ema_nchw,
                               source_logits=source_logits, target_logits=target_logits)
+        if rec_m is not None:
+            self.last_step.update(masked_img=masked_img, mask_grid=mask_u)
+            if self.mic:
+                self.last_step['masked_logits'] = masked_logits
         outs = _TrainStepFn.apply(state, len(names), *[losses[n] for n in names], *params)
         return dict(zip(names, outs))
 
@@ -401,7 +450,8 @@ class MTMADISE(MadmInference):
 
 class _TrainStepFn(torch.autograd.Function):
     """The whole training forward as ONE autograd node: outputs = the loss scalars the HIP forward computed, inputs = every
-    trainable parameter; backward = the explicit gradient kernels over the two recorded student passes, each loss weighted
+    trainable parameter; backward = the explicit gradient kernels over the two (three with masked image consistency)
+    recorded student passes, each loss weighted
     by the gradient that reaches it (sum of the losses, GradScaler scale, per-loss weights -- all stay device scalars)."""
 
     @staticmethod
@@ -428,9 +478,14 @@ class _TrainStepFn(torch.autograd.Function):
         passes = []                                  # finished spans are all-reduced while the backward still runs
         dtype = st["rec_s"]["keep"]["dtype"]
         for rec, ce_name, dec_name in ((st["rec_s"], 'source_loss', 'vae_decoder_source_loss'),
-                                       (st["rec_t"], 'target_loss', 'vae_decoder_target_loss')):
-            if (g.get(ce_name) is not None) or (dec_name in ctxs and g.get(dec_name) is not None):
+                                       (st["rec_t"], 'target_loss', 'vae_decoder_target_loss'),
+                                       (st["rec_m"], 'masked_prompt_consistency_loss', 'mic_vae_decoder_loss')):
+            if rec is None:
+                continue
+            if (ce_name in ctxs and g.get(ce_name) is not None) or (dec_name in ctxs and g.get(dec_name) is not None):
                 passes.append((rec, ce_name, dec_name))
+        # gradient sink: a parameter's span is finished by the LAST pass that runs (final); the earlier ones accumulate, and
+        # what only they touched is finished after the walk
         for i, (rec, ce_name, dec_name) in enumerate(passes):
             last = i == len(passes) - 1
 
@@ -448,7 +503,9 @@ class _TrainStepFn(torch.autograd.Function):
                 cur = acc.get(id(p))
                 acc[id(p)] = v if cur is None else cur + v
 
-            dlogits = crit.ce_backward(ctxs[ce_name], g[ce_name], dtype) if g.get(ce_name) is not None else None
+            dlogits = None
+            if ce_name in ctxs and g.get(ce_name) is not None:
+                dlogits = crit.ce_backward(ctxs[ce_name], g[ce_name], dtype)
             dsample = None
             if dec_name in ctxs and g.get(dec_name) is not None:
                 dsample = crit.decoder_loss_backward(ctxs[dec_name], g[dec_name])
@@ -469,7 +526,7 @@ class _TrainStepFn(torch.autograd.Function):
                         acc[id(p)] = torch.zeros_like(p)
                     else:
                         early.add(id(p))       # the flat gradient buffer is already zero: only mark the span finished
-        st["rec_s"] = st["rec_t"] = None       # free the tapes
+        st["rec_s"] = st["rec_t"] = st["rec_m"] = None       # free the tapes
         model.last_grad_param_ids = touched    # torch.optim.AdamW skips parameters whose grad is None
         if sink is not None:
             for p in params:                   # gradients only the first pass produced: already added, now finished

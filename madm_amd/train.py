@@ -2,7 +2,7 @@
 (/root/reference/engine/train_loop.py:257-311) -- autocast forward, ``model.zero_grad()``, ``scaler.scale(losses)
 .backward()``, unscale, ``clip_grad_norm_``, ``optimizer.step()``, ``scaler.update()`` -- on flat storage:
 
-    losses = model(data)                      HIP forward (3 passes), loss scalars = outputs of ONE autograd node
+    losses = model(data)                      HIP forward (3 or 4 passes), loss scalars = outputs of ONE autograd node
     (scale * sum(losses)).backward()          explicit HIP backward; gradients accumulate into ONE flat fp32 buffer
     all-reduce(mean)                          dist.GradBucketReducer over that buffer (DDP's only job; world > 1)
     clip + AdamW                              optim.TableAdamW: ONE launch, per-tensor lr / weight decay / step
@@ -141,12 +141,18 @@ class MadmTrainer:
         ldm = self._ldm
         if ldm is not None and ldm.check_input_range:
             ldm.deferred_range_probes = []        # the three passes' range asserts (ldm_diffusers.py:147): checked at the step's end
+        mic = hasattr(model, "deferred_mask_flags")
+        if mic:
+            model.deferred_mask_flags = []        # mask_image's range assert (dacs_transforms.py:163), likewise
         try:
             loss_dict = model(data)
         finally:
             probes = [] if ldm is None else (ldm.deferred_range_probes or [])
             if ldm is not None:
                 ldm.deferred_range_probes = None
+            mask_flags = (model.deferred_mask_flags or []) if mic else []
+            if mic:
+                model.deferred_mask_flags = None
         losses = sum(loss_dict.values())
         (losses * self.scale).backward()
         self.flush()
@@ -169,6 +175,9 @@ class MadmTrainer:
                 lo, hi = mm.tolist()
                 assert -1 <= lo and hi <= 1, \
                     f"input range check (ldm_diffusers.py:147), forward pass {i} of this step: min {lo} max {hi}"
+            for flag in mask_flags:
+                assert int(flag.item()) == 0, \
+                    "BlockMaskGenerator.mask_image (dacs_transforms.py:163): the image batch lies outside [0, 255]"
 
         norm, stepped = self.opt.step(clip_grad=self.grad_clip, loss_scale=self.scale, touched=touched, on_synced=check_probes)
         if self.amp:
