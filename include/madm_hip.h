@@ -582,6 +582,23 @@ int madm_block_mask(const float* in, float* out, int B, int C, int H, int W, con
 int madm_tanh_gate_bwd(const float* a1, const float* x1, const float* a2, const float* x2, const float* dout, float* da1,
                        float* dx1, float* da2, float* dx2, size_t n, int repeat, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * CLIP text encoder (HF CLIPTextModel, the SD-v1-4 text tower the reference runs once on '' at construction,
+ * modeling/meta_arch/ldm_diffusers.py:219-243).  Always f32: the reference runs it in fp32 outside autocast.  The
+ * projections, folded LayerNorms and the final LayerNorm are madm_conv2d_fwd / madm_layernorm_fwd launches.
+ * ------------------------------------------------------------------------------- */
+/* out[n*L + i][:] = tok[ids[n][i]][:] + pos[i][:] (f32 [N*L][C]); ids int64 [N][L], tok [vocab][C], pos [n_pos][C],
+ * L <= n_pos.  Ids are range-checked by the caller; an id outside [0, vocab) yields a NaN row, never a read. */
+int madm_token_embedding(const int64_t* ids, int N, int L, const float* tok, int vocab, const float* pos, int n_pos,
+                         int C, float* out, void* stream);
+/* Causal self-attention, the madm_attention_fwd addressing (q / k / v / o rows b*L + i, head h at column h*D, row strides
+ * ldq / ldk / ldv / ldo: column windows of one fused [M, 3*H*D] QKV output work): o_i = sum_{j <= i} softmax_j(scale
+ * q_i . k_j) v_j, key j > i gets exactly zero weight; statistics in f32.  Requires dtype MADM_F32, D == 64 and
+ * Lq == Lk <= 128. */
+int madm_causal_attention_fwd(const madm_attention_args* a, void* stream);
+/* y = x * sigmoid(1.702 x) (CLIP's quick_gelu), evaluated in f32; dtype storage, in place allowed. */
+int madm_quick_gelu(int dtype, const void* x, void* y, size_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,9 @@ SYMBOLS = [
                                 c_float, c_void_p, c_int, c_void_p, c_void_p]),
     ("madm_tanh_gate_bwd", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_size_t, c_int, c_void_p]),
+    ("madm_token_embedding", c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    ("madm_causal_attention_fwd", c_int, [ctypes.POINTER(AttentionArgs), c_void_p]),
+    ("madm_quick_gelu", c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 ]
 
 

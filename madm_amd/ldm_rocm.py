@@ -264,6 +264,8 @@ class LdmRocm(nn.Module):
         self.compute_dtype = compute_dtype
         self.check_input_range = check_input_range
         self.deferred_range_probes = None     # a list: forward passes append their (min, max) probe instead of syncing on it
+        self._device = torch.device(device)   # where the construction-time text encoder runs (the model moves there below)
+        self._text_encoder = None             # built by embed_text; kept OUT of the module tree (state_dict, parameters)
 
         self.vae = AutoencoderKL()
         self.unet = UNet2DConditionModel()
@@ -349,16 +351,38 @@ class LdmRocm(nn.Module):
                 p.requires_grad = False
 
     def _get_uncond_inputs(self, text):
-        """ldm_diffusers.py:219-243 runs the CLIP text encoder on '' once at construction.  The text
-        encoder is outside the hot path and its weights are not available offline: a precomputed
-        ``uncond_inputs.pt`` next to the snapshot is used when present, otherwise a seeded stand-in
-        of the prompt-embedding scale (ldm_base.py:653)."""
+        """ldm_diffusers.py:219-243 runs the CLIP text encoder on '' once at construction.  In order: a precomputed
+        ``uncond_inputs.pt`` next to the snapshot; the snapshot's ``text_encoder/`` + ``tokenizer/`` run by the HIP
+        encoder (madm_amd/clip_text.py; a non-CUDA ``device`` raises, there is no CPU path), its weights released again
+        afterwards; otherwise (no snapshot files: synthetic setups) a seeded stand-in of the prompt-embedding scale
+        (ldm_base.py:653)."""
+        from . import clip_text
         p = os.path.join(self.stable_diffusion_name_or_path, "uncond_inputs.pt")
         if self.stable_diffusion_name_or_path and os.path.exists(p):
             t = torch.load(p, map_location="cpu").float()
             assert tuple(t.shape) == tuple(self.uncond_inputs_size)
             return t
+        if clip_text.has_text_encoder(self.stable_diffusion_name_or_path):
+            t = clip_text.TextEncoder(self.stable_diffusion_name_or_path, self._device)([text])
+            assert tuple(t.shape) == tuple(self.uncond_inputs_size), (tuple(t.shape), tuple(self.uncond_inputs_size))
+            return t
         return 0.02 * torch.randn(*self.uncond_inputs_size, generator=torch.Generator().manual_seed(4242))
+
+    def embed_text(self, texts):
+        """CLIP ``last_hidden_state`` (after ``final_layer_norm``) of ``texts``: f32 [N, 77, 768] on the model's device,
+        computed by the HIP encoder from the snapshot's ``text_encoder/`` and ``tokenizer/`` (built on the first call,
+        then kept outside the module tree: ``state_dict()`` / ``parameters()`` do not change).  Raises when either
+        directory is missing or the model is not on a CUDA device."""
+        from . import clip_text
+        if isinstance(texts, str):
+            texts = [texts]
+        dev = self.shared_noise.device
+        enc = self._text_encoder
+        if enc is None or enc.device != dev:
+            enc = self._text_encoder = None
+            enc = clip_text.TextEncoder(self.stable_diffusion_name_or_path, dev)
+            self._text_encoder = enc
+        return enc(texts)
 
     def forward(self, batched_inputs, input_modal, **kwargs):
         # two stages with a narrow hand-over (the noisy latents), so that a serving loop can capture / schedule them

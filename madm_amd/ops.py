@@ -752,6 +752,51 @@ def attention(q, k, v, B, H, Lq, Lk, D, scale, out=None):
     return out
 
 
+def causal_attention(q, k, v, B, H, L, D, scale, out=None):
+    """Causal self-attention of the CLIP text encoder (madm_causal_attention_fwd): f32 q / k / v [B*L, >=H*D] views with unit
+    column stride (e.g. column windows of one fused QKV output); key j > i gets zero weight.  Returns o [B*L, H*D] f32."""
+    _need_cuda(q, k, v, out)
+    for t in (q, k, v):
+        assert t.stride(1) == 1 and t.dtype == torch.float32 and t.shape[0] == B * L and t.shape[1] >= H * D
+    if out is None:
+        out = torch.empty((B * L, H * D), dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and out.stride(1) == 1 and tuple(out.shape) == (B * L, H * D)
+    a = AttentionArgs()
+    a.dtype = MADM_F32
+    a.q, a.k, a.v, a.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
+    a.B, a.H, a.Lq, a.Lk, a.D = B, H, L, L, D
+    a.scale = float(scale)
+    with _Prof(f"causal_attn_d{D}_f32", 2.0 * B * H * L * (L + 1) * D, f"B{B} H{H} L{L}"):
+        check(lib.madm_causal_attention_fwd(ctypes.byref(a), _stream()), "madm_causal_attention_fwd")
+    return out
+
+
+def token_embedding(ids, tok, pos):
+    """ids int64 [N, L] (device, already range-checked), tok f32 [vocab, C], pos f32 [n_pos, C] -> f32 [N*L, C]."""
+    _need_cuda(ids, tok, pos)
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.is_contiguous()
+    assert tok.dtype == torch.float32 and pos.dtype == torch.float32 and tok.is_contiguous() and pos.is_contiguous()
+    N, L = ids.shape
+    C = tok.shape[1]
+    assert pos.shape[1] == C
+    out = torch.empty((N * L, C), dtype=torch.float32, device=tok.device)
+    check(lib.madm_token_embedding(ids.data_ptr(), N, L, tok.data_ptr(), tok.shape[0], pos.data_ptr(), pos.shape[0], C,
+                                   out.data_ptr(), _stream()), "madm_token_embedding")
+    return out
+
+
+def quick_gelu(x, out=None):
+    """x * sigmoid(1.702 x), f32 arithmetic (CLIP's MLP activation)."""
+    _need_cuda(x, out)
+    assert x.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.is_contiguous() and out.dtype == x.dtype and out.shape == x.shape
+    check(lib.madm_quick_gelu(dtype_code(x), x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "madm_quick_gelu")
+    return out
+
+
 def attention_backward(q, k, v, o, dout, B, H, Lq, Lk, D, scale, outs=None):
     """Backward of :func:`attention`: q / k / v / o / dout as in the forward (row-strided views with unit column
     stride); returns (dq [B*Lq, H*D], dk [B*Lk, H*D], dv [B*Lk, H*D]) -- dense, or the row-strided views given
