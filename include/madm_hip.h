@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MADM_ABI_VERSION 5
+#define MADM_ABI_VERSION 6
 
 typedef enum {
     MADM_OK = 0,
@@ -145,7 +145,7 @@ typedef struct {
      * variance from them and stores out = act((v - mean) * rstd * pn_gamma[n] + pn_beta[n]): the raw conv output never
      * reaches memory and the stand-alone reduction + GroupNorm passes become one launch.  pn_gamma NULL = off.  Needs the
      * effective splitk > 1, the plain epilogue, no residual / stats / out_f32, N / pn_groups even and the group's values
-     * within 96 KB of LDS (madm_conv2d_can_post_groupnorm tells). */
+     * within 96 KB of LDS (madm_conv2d_plan.post_gn tells). */
     const float* pn_gamma;
     const float* pn_beta;
     int pn_groups;
@@ -153,25 +153,26 @@ typedef struct {
     int pn_act;           /* madm_act */
 } madm_conv2d_args;
 
-size_t madm_conv2d_workspace_bytes(const madm_conv2d_args* a);
-/* heuristic split-K for the MI355X grid (256 CUs); returns 1 when the tile grid already fills it */
-int madm_conv2d_suggest_splitk(const madm_conv2d_args* a);
 int madm_conv2d_fwd(const madm_conv2d_args* a, void* stream);
 /* 1 when these arguments can take gn_sums1 / gn_gamma / ... (the LDS halo-tile 3x3 kernel applies), else 0. */
 int madm_conv2d_can_fuse_groupnorm(const madm_conv2d_args* a);
-/* 1 when madm_conv2d_fwd with these arguments (splitk, dims, pn_groups set; pointers not needed) can take pn_gamma / ...,
- * else 0. */
-int madm_conv2d_can_post_groupnorm(const madm_conv2d_args* a);
-/* which kernel instance madm_conv2d_fwd will launch for these arguments: 1 = igemm 128x128,
- * 2 = igemm 128x64, 3 = igemm 64x64, 4 = halo conv3x3 x128 channels, 5 = halo conv3x3 x64 channels,
- * 6 = igemm 64x64 with the 8-deep prefetch, 7 / 8 = LDS-DMA igemm 64x64 / 128x64,
- * 9 / 10 = halo conv3x3 x128 / x64 with LDS-DMA weights, 11 = LDS-DMA igemm 64x64 with the short ring
- * (used by bench.py to attribute time). */
-int madm_conv2d_pick_tile(const madm_conv2d_args* a);
-/* 1 when a row of the tuned table (madm_amd/csrc/igemm_tuned.inc, MADM_TUNED_FILE) decides this launch's tile / split-K, 0 when
- * it falls through to the heuristics (tests/test_parity_gpu.py::test_bench_workloads_have_tuned_rows: a shape of the bench
- * workloads without a row ran 2 x too long for a whole round). */
-int madm_conv2d_has_tuned_row(const madm_conv2d_args* a);
+
+/* Everything that is decided about one launch (ABI 6), from ONE reading of the tuning profile and the tile override.  The request
+ * is a madm_conv2d_args with the dims, flags and the optional pointers that shape the choice (no tensor is touched), where
+ * splitk 0 = the library chooses (>= 1 = forced), pn_groups > 0 = carry the consumer's GroupNorm if this launch can, stats
+ * non-NULL = output statistics are wanted where it cannot.  The caller sets splitk, a workspace and EITHER pn_gamma / pn_beta /
+ * pn_eps / pn_act (post_gn == 1) OR stats accordingly and calls madm_conv2d_fwd, which resolves tile and split-K by the same code. */
+typedef struct {
+    int tile;               /* kernel instance, 1..17: the table g_tiles of madm_amd/csrc/igemm.hip */
+    int splitk;             /* to pass to madm_conv2d_fwd */
+    int splitk_eff;         /* what the kernels run with: splitk clamped to the K steps (halo kernels: channel chunks) */
+    int post_gn;            /* 1: the split-K reduction carries the GroupNorm of pn_groups */
+    int tuned_row;          /* 1: a row of the tuned tables (igemm_tuned*.inc, MADM_TUNED_FILE) was found for the shape, 0: heuristics
+                             * (test_bench_workloads_have_tuned_rows: a bench shape without a row ran 2 x too long) */
+    size_t workspace_bytes; /* f32 [splitk][M][N]; 0 without split-K */
+} madm_conv2d_plan;
+int madm_conv2d_make_plan(const madm_conv2d_args* request, madm_conv2d_plan* plan);
+const char* madm_conv2d_tile_name(int tile);   /* bench.py's name of the tile's kernel class; NULL for an unknown code */
 /* Tile / split-K table profile of the process (ABI 5): 0 = throughput -- the rows tuned with the layer's launches side by side on three
  * streams, the default and what the graph runners of madm_amd/pipeline.py capture under; 1 = latency -- rows tuned for one launch on an
  * idle chip are consulted first (a synchronous caller with one batch in flight: the reference's own loop,
@@ -179,7 +180,7 @@ int madm_conv2d_has_tuned_row(const madm_conv2d_args* a);
 int madm_set_tuning_profile(int profile);
 int madm_get_tuning_profile(void);
 /* tuning/debug aid: force the workgroup tile (0 = tuned table then heuristic, -1 = heuristic only,
- * 1..11 = the tile codes of madm_conv2d_pick_tile). */
+ * 1..17 = the tile codes of madm_conv2d_plan). */
 void madm_debug_set_conv_tile(int tile);
 /* test aid: fills the LDS of every CU with `pattern` (0x7fc00000 = quiet NaN) -- a kernel that reads LDS it has not written then
  * fails deterministically instead of depending on its predecessor on the CU.  sink: 4 bytes of device memory, never written. */

@@ -59,6 +59,10 @@ class Conv2dArgs(ctypes.Structure):
     ]
 
 
+class Conv2dPlan(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("tile", "splitk", "splitk_eff", "post_gn", "tuned_row")] + [("workspace_bytes", c_size_t)]
+
+
 class Conv2dWgradArgs(ctypes.Structure):
     _fields_ = [
         ("dtype", c_int),
@@ -104,14 +108,11 @@ SYMBOLS = [
     ("madm_abi_version", c_int, []),
     ("madm_last_error", ctypes.c_char_p, []),
     ("madm_calib_mfma_loop", c_int, [c_int, c_int, c_void_p, ctypes.POINTER(ctypes.c_double), c_void_p]),
-    ("madm_conv2d_workspace_bytes", c_size_t, [ctypes.POINTER(Conv2dArgs)]),
-    ("madm_conv2d_suggest_splitk", c_int, [ctypes.POINTER(Conv2dArgs)]),
-    ("madm_conv2d_pick_tile", c_int, [ctypes.POINTER(Conv2dArgs)]),
-    ("madm_conv2d_has_tuned_row", c_int, [ctypes.POINTER(Conv2dArgs)]),
+    ("madm_conv2d_make_plan", c_int, [ctypes.POINTER(Conv2dArgs), ctypes.POINTER(Conv2dPlan)]),
+    ("madm_conv2d_tile_name", ctypes.c_char_p, [c_int]),
     ("madm_set_tuning_profile", c_int, [c_int]),
     ("madm_get_tuning_profile", c_int, []),
     ("madm_conv2d_can_fuse_groupnorm", c_int, [ctypes.POINTER(Conv2dArgs)]),
-    ("madm_conv2d_can_post_groupnorm", c_int, [ctypes.POINTER(Conv2dArgs)]),
     ("madm_groupnorm_finalize", c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                         c_float, c_void_p, c_void_p, c_void_p]),
     ("madm_conv2d_fwd", c_int, [ctypes.POINTER(Conv2dArgs), c_void_p]),

@@ -8,6 +8,7 @@
 // t+1 are issued before the MFMAs of tile t and written to the other buffer after them; one
 // barrier per K-tile.  The MFMA is issued as D = W_frag x A_frag so that every lane ends up with
 // 4 CONSECUTIVE output channels of one pixel: 8/16-byte stores, vector bias / residual loads.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -806,11 +807,30 @@ __global__ __launch_bounds__(PGN_THREADS) void splitk_groupnorm_kernel(const Ige
     }
 }
 
-// can the split-K reduction of this launch apply the consumer's GroupNorm?  (mirrors the clamps of madm_conv2d_fwd)
+// LDS of one (image, group) workgroup of splitk_groupnorm_kernel
 inline size_t post_gn_lds(int HW, int N, int G) { return (size_t)HW * (size_t)(N / G) * sizeof(float); }
 
-int g_tile_override = 0;  // 0 = tuned table then heuristic; -1 = heuristic only; 1..6 = forced tile code
-inline bool is_igemm_tile(int t) { return t <= 3 || (t >= 6 && t <= 8) || t == 11 || (t >= 14 && t <= 17); }
+// The tile codes of madm_conv2d_plan.tile, the tuned tables and madm_debug_set_conv_tile; the names are bench.py's kernel classes.
+// IGEMM = register-staged implicit GEMM, `slots` deep (6: for latency-bound small-M GEMMs streaming cold weights); GLDS = fed by
+// LDS-DMA through a ring of `slots` stages (+ the 3 KB constant stash of every instantiation: 11 and 17 = 51 KB, three blocks per
+// CU; 16 = 35 KB, four, whose prologues and epilogues cover each other on short-K layers; 14 / 15 = 99 / 67 KB, 8 KB of operands
+// per MFLOP instead of 11 (128x64) / 31 (64x64): few fat workgroups for launches whose neighbours are other streams' kernels);
+// HALO / HALO_DMA = 3x3 conv on 8 x 16-pixel halo patches, weights through registers / LDS-DMA; H16 = 16 x 16-pixel patches, all
+// by LDS-DMA, folds a 2x upsample (maps >= 16 x 16); APANEL = A-stationary linear layer (BM / BN only feed the split-K heuristic)
+enum TileFamily { IGEMM, GLDS, HALO, HALO_DMA, H16, APANEL };
+struct Tile { int code, bm, bn; TileFamily family; int slots; const char* name; };
+constexpr Tile g_tiles[] = {
+    {1, 128, 128, IGEMM, 2, "igemm_128x128"},        {2, 128, 64, IGEMM, 3, "igemm_128x64"},          {3, 64, 64, IGEMM, 4, "igemm_64x64"},
+    {4, 128, 128, HALO, 0, "conv3x3_halo_x128"},     {5, 128, 64, HALO, 0, "conv3x3_halo_x64"},       {6, 64, 64, IGEMM, 8, "igemm_64x64d"},
+    {7, 64, 64, GLDS, 4, "igemm_glds_64x64"},        {8, 128, 64, GLDS, 3, "igemm_glds_128x64"},      {9, 128, 128, HALO_DMA, 0, "conv3x3_halo_dma_x128"},
+    {10, 128, 64, HALO_DMA, 0, "conv3x3_halo_dma_x64"}, {11, 64, 64, GLDS, 3, "igemm_glds_64x64s"},   {12, 256, 128, H16, 0, "conv3x3_h16_x128"},
+    {13, 64, 64, APANEL, 0, "igemm_apanel"},         {14, 128, 128, GLDS, 3, "igemm_glds_128x128"},   {15, 128, 128, GLDS, 2, "igemm_glds_128x128d"},
+    {16, 64, 64, GLDS, 2, "igemm_glds_64x64d"},      {17, 128, 64, GLDS, 2, "igemm_glds_128x64d"}};
+constexpr int N_TILES = sizeof g_tiles / sizeof g_tiles[0];
+inline const Tile* tile_info(int t) { return t >= 1 && t <= N_TILES && g_tiles[t - 1].code == t ? &g_tiles[t - 1] : nullptr; }
+inline bool is_igemm_tile(int t) { const Tile* i = tile_info(t); return i && (i->family == IGEMM || i->family == GLDS); }
+inline bool is_halo_tile(int t) { const Tile* i = tile_info(t); return i && i->family >= HALO && i->family <= H16; }
+int g_tile_override = 0;  // 0 = tuned table then heuristic; -1 = heuristic only; 1..N_TILES = forced tile code
 // tile 13 (igemm_apanel.hip): plain linear layer, one source, whole rows resident: no split-K, no residual / time row /
 // fused output statistics (its epilogue touches no global memory but the stores)
 inline bool apanel_eligible(const madm_conv2d_args* a) {
@@ -820,7 +840,6 @@ inline bool apanel_eligible(const madm_conv2d_args* a) {
            // its stores go through a buffer descriptor with 32-bit offsets (0x80000000 = "drop this lane")
            (size_t)a->B * a->OH * a->OW * (size_t)a->ldo * (a->out_f32 ? 4 : madm_esize(a->dtype)) < 0x80000000ull;
 }
-inline bool is_halo_tile(int t) { return t == 4 || t == 5 || t == 9 || t == 10 || t == 12; }
 
 // Launch configurations measured on MI355X by tools/tune_insitu.py for the layer shapes of the SD-v1-4
 // feature extractor at bs=2, 512x512 (any other shape falls back to the heuristics below).
@@ -858,8 +877,8 @@ const std::vector<Tuned>& tuned_overrides() {
             if (sscanf(line, "%d %d %d %d %d %d %d %d", &t.dtype, &t.M, &t.N, &t.K, &t.KH, &t.variant, &t.tile, &t.splitk) != 8)
                 continue;
             // a row with an unknown tile code would fall through to the default igemm launch unnoticed: refuse it loudly
-            if (t.tile < 1 || t.tile > 17 || t.splitk < 1 || t.variant < 0 || t.variant > 3 || !madm_dtype_ok(t.dtype)) {
-                fprintf(stderr, "madm: MADM_TUNED_FILE=%s: row ignored (tile 1..17, splitk >= 1, variant 0..3): %s", path, line);
+            if (!tile_info(t.tile) || t.splitk < 1 || t.variant < 0 || t.variant > 3 || !madm_dtype_ok(t.dtype)) {
+                fprintf(stderr, "madm: MADM_TUNED_FILE=%s: row ignored (tile 1..%d, splitk >= 1, variant 0..3): %s", path, N_TILES, line);
                 continue;
             }
             v.push_back(t);
@@ -870,18 +889,31 @@ const std::vector<Tuned>& tuned_overrides() {
     return rows;
 }
 
-const Tuned* find_tuned(int dtype, int M, int N, int K, int KH, int variant) {
-    if (dtype == MADM_F16) dtype = MADM_BF16;   // same kernels, same instruction rate: the bf16 table serves both
-    if (g_tile_override != 0) return nullptr;
-    for (const Tuned& t : tuned_overrides())
-        if (t.dtype == dtype && t.M == M && t.N == N && t.K == K && t.KH == KH && t.variant == variant) return &t;
-    if (g_tuning_profile.load(std::memory_order_relaxed) == 1)
-        for (const Tuned* t = g_tuned_latency; t->dtype >= 0; ++t)
-            if (t->dtype == dtype && t->M == M && t->N == N && t->K == K && t->KH == KH && t->variant == variant) return t;
-    for (const Tuned* t = g_tuned; t->dtype >= 0; ++t)
-        if (t->dtype == dtype && t->M == M && t->N == N && t->K == K && t->KH == KH && t->variant == variant) return t;
-    return variant == 3 ? find_tuned(dtype, M, N, K, KH, 0) : nullptr;
-}
+// One conv2d request while it is being decided: the arguments as they stand at this stage of the decision, the GEMM they
+// describe, and the two process-wide knobs, read ONCE -- every tile / split-K question of one launch is answered from here.
+struct Request {
+    const madm_conv2d_args* a;
+    int M, K;                     // B OH OW, KH KW (C1 + C2)
+    int tile_override, profile;   // g_tile_override, g_tuning_profile
+    explicit Request(const madm_conv2d_args* args)
+        : a(args), M(args->B * args->OH * args->OW), K(args->KH * args->KW * (args->C1 + args->C2)),
+          tile_override(g_tile_override), profile(g_tuning_profile.load(std::memory_order_relaxed)) {}
+    int k_steps() const { return K / (8 * madm_epc(a->dtype)); }
+    int channel_chunks() const { return (a->C1 + a->C2) / (8 * madm_epc(a->dtype)); }
+    // the table row of this shape under `variant`: run-time rows, then the latency rows under profile 1, then the throughput table
+    const Tuned* row(int variant) const {
+        if (tile_override != 0) return nullptr;
+        const int dt = a->dtype == MADM_F16 ? MADM_BF16 : a->dtype;   // same kernels, same instruction rate: the bf16 table serves both
+        auto hit = [&](const Tuned& t) { return t.dtype == dt && t.M == M && t.N == a->N && t.K == K && t.KH == a->KH && t.variant == variant; };
+        for (const Tuned& t : tuned_overrides())
+            if (hit(t)) return &t;
+        for (const Tuned* t = g_tuned_latency; profile == 1 && t->dtype >= 0; ++t)
+            if (hit(*t)) return t;
+        for (const Tuned* t = g_tuned; t->dtype >= 0; ++t)
+            if (hit(*t)) return t;
+        return variant == 3 ? row(0) : nullptr;
+    }
+};
 
 int heuristic_tile(int M, int N, int K) {
     auto tiles = [&](int bm, int bn) { return (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
@@ -892,8 +924,8 @@ int heuristic_tile(int M, int N, int K) {
     return 3;
 }
 
-// narrowest map the halo kernels take (env MADM_HALO_MIN_W for A/B runs; ops.can_fuse_groupnorm mirrors it): an 8-wide
-// map wastes half of every 8 x 16 patch, but lets the 8 x 8 UNet level fuse its GroupNorm
+// narrowest map the halo kernels take (env MADM_HALO_MIN_W for A/B runs): an 8-wide map wastes half of every 8 x 16 patch,
+// but lets the 8 x 8 UNet level fuse its GroupNorm
 int halo_min_width() {
     static const int w = [] { const char* e = getenv("MADM_HALO_MIN_W"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : v; }();
     return w;
@@ -905,31 +937,23 @@ bool halo_eligible(const madm_conv2d_args* a) {
            a->OH == a->IH && a->OW == a->IW && a->OH >= 8 && a->OW >= halo_min_width() && a->epilogue != MADM_EPI_GEGLU;
 }
 
-// tile codes: 1 = igemm 128x128, 2 = igemm 128x64, 3 = igemm 64x64, 4 = halo conv3x3 BN=128, 5 = halo BN=64,
-// 6 = igemm 64x64 with an 8-deep register prefetch (latency-bound small-M GEMMs streaming cold weights),
-// 7 / 8 = LDS-DMA igemm 64x64 (4-slot ring) / 128x64 (3-slot ring), 9 / 10 = halo BN=128 / BN=64 with LDS-DMA weights,
-// 11 = LDS-DMA igemm 64x64 with a 3-slot ring (48 KB + the 3 KB constant stash of every igemm_glds instantiation = 51 KB:
-//      three blocks per CU use 153 of the 160 KB, for grids of 513 .. 768 tiles),
-// 12 = halo conv3x3 on 16 x 16-pixel patches, BN = 128, halo and weights by LDS-DMA (conv3x3_h16.hip; maps >= 16 x 16),
-// 14 / 15 = LDS-DMA igemm 128x128 with a 3-slot (96 + 3 KB, one block per CU) / 2-slot ring (64 + 3 KB, two blocks per CU): 8 KB of
-// operands per MFLOP through the CU's load path instead of 11 (128x64) / 31 (64x64) -- few, fat workgroups for launches
-// whose neighbours on the chip are other streams' kernels (tools/tune_concurrent.py)
-int pick_tile_raw(const madm_conv2d_args* a) {
-    const int M = a->B * a->OH * a->OW, K = a->KH * a->KW * (a->C1 + a->C2);
+int pick_tile_raw(const Request& r) {
+    const madm_conv2d_args* a = r.a;
+    const int forced = r.tile_override;
     const bool halo_ok = halo_eligible(a);
     const int halo_default = (a->N % 128 == 0 || a->N >= 512) ? 4 : 5;
     if (a->gn_sums1) {   // fused GroupNorm exists only in the halo kernels
-        if (is_halo_tile(g_tile_override)) return g_tile_override;
-        if (const Tuned* t = find_tuned(a->dtype, M, a->N, K, a->KH, variant_of(a)))
+        if (is_halo_tile(forced)) return forced;
+        if (const Tuned* t = r.row(variant_of(a)))
             if (is_halo_tile(t->tile)) return t->tile;
         return halo_default;
     }
-    if (g_tile_override > 0 && (is_igemm_tile(g_tile_override) || (is_halo_tile(g_tile_override) && halo_ok)))
-        return g_tile_override;   // (13 = the A-stationary kernel is handled by pick_tile; ineligible launches fall through)
-    if (const Tuned* t = find_tuned(a->dtype, M, a->N, K, a->KH, variant_of(a)))
+    if (is_igemm_tile(forced) || (is_halo_tile(forced) && halo_ok))
+        return forced;   // (13 = the A-stationary kernel is handled by pick_tile; ineligible launches fall through)
+    if (const Tuned* t = r.row(variant_of(a)))
         if (is_igemm_tile(t->tile) || halo_ok) return t->tile;
-    if (halo_ok && M >= 2048) return halo_default;
-    return heuristic_tile(M, a->N, K);
+    if (halo_ok && r.M >= 2048) return halo_default;
+    return heuristic_tile(r.M, a->N, r.K);
 }
 
 // the 16 x 16-patch kernel pays where it fills the chip: at least ~0.75 rounds of its 256-pixel x 128-channel blocks
@@ -949,44 +973,58 @@ bool h16_upsample_eligible(const madm_conv2d_args* a) {
            a->OW >= 16;
 }
 
-int pick_tile(const madm_conv2d_args* a) {
-    if (apanel_eligible(a)) {
-        if (g_tile_override == 13) return 13;
-        if (g_tile_override == 0) {
-            const int M = a->B * a->OH * a->OW;
-            if (const Tuned* t = find_tuned(a->dtype, M, a->N, a->C1, 1, 0))
-                if (t->tile == 13) return 13;
-        }
+int pick_tile(const Request& r) {
+    const madm_conv2d_args* a = r.a;
+    if (apanel_eligible(a)) {   // (K = C1, KH = 1, variant 0)
+        if (r.tile_override == 13) return 13;
+        if (const Tuned* t = r.row(0))
+            if (t->tile == 13) return 13;
     }
     if (h16_upsample_eligible(a)) {
-        if (g_tile_override == 12) return 12;
-        if (g_tile_override == 0) {
-            // a table row decides (variant 2; the side-by-side tuner put the UNet's upsample convs here although their grids
-            // are far below a round of workgroups), h16_pays() where there is none
-            const int M = a->B * a->OH * a->OW, K = a->KH * a->KW * (a->C1 + a->C2);
-            if (const Tuned* t = find_tuned(a->dtype, M, a->N, K, a->KH, 2)) {
-                if (t->tile == 12) return 12;
-            } else if (h16_pays(a)) {
-                return 12;
-            }
-        }
+        // a table row decides (variant 2; the side-by-side tuner put the UNet's upsample convs here although their grids
+        // are far below a round of workgroups), h16_pays() where there is none; no row is looked up under a tile override
+        const Tuned* t = r.row(2);
+        if (r.tile_override == 12 || (t ? t->tile == 12 : (r.tile_override == 0 && h16_pays(a)))) return 12;
     }
-    const int t = pick_tile_raw(a);
+    const int t = pick_tile_raw(r);
     if (t == 12 && (a->OH < 16 || a->OW < 16)) return 9;   // the 16 x 16-patch kernel needs a map of at least one patch
-    if ((t == 4 || t == 9) && g_tile_override == 0 && h16_pays(a)) return 12;
+    if ((t == 4 || t == 9) && r.tile_override == 0 && h16_pays(a)) return 12;
     return t;
 }
 
-void tile_dims(int t, int& bm, int& bn) {
-    if (t == 12) { bm = 256; bn = 128; }
-    else if (t == 1 || t == 4 || t == 9 || t == 14 || t == 15) { bm = 128; bn = 128; }
-    else if (t == 2 || t == 5 || t == 8 || t == 10 || t == 17) { bm = 128; bn = 64; }
-    else { bm = 64; bn = 64; }
+// split-K for the 256 CUs of MI355X where the request leaves it to the library: the row's if its tile is the one chosen, else about two rounds
+int suggest_splitk(const Request& r) {
+    const int chosen = pick_tile(r), nk = r.k_steps();
+    if (const Tuned* t = r.row(variant_of(r.a)))
+        if (t->tile == chosen) return t->splitk;
+    const Tile* ti = tile_info(chosen);
+    const long long tiles = (long long)((r.M + ti->bm - 1) / ti->bm) * ((r.a->N + ti->bn - 1) / ti->bn);
+    if (tiles >= 192 || nk < 8) return 1;
+    return (int)std::max(1LL, std::min({(512 + tiles - 1) / tiles, nk / 4LL, 32LL}));
 }
 
-int fill_params(const madm_conv2d_args* a, IgemmP& p) {
-    MADM_REQUIRE(a != nullptr, "conv2d: null args");
-    MADM_REQUIRE(madm_dtype_ok(a->dtype), "conv2d: bad dtype %d", a->dtype);
+inline size_t splitk_workspace_bytes(int sk, const Request& r) { return sk > 1 ? (size_t)sk * (size_t)r.M * (size_t)r.a->N * sizeof(float) : 0; }
+
+// the arguments taken as they stand: the tile madm_conv2d_fwd launches and the split-K its kernels run with (at least one K step
+// per slice; the halo kernels split K by whole channel chunks)
+void resolve(const Request& r, madm_conv2d_plan& pl) {
+    pl.tile = pick_tile(r);
+    pl.splitk = r.a->splitk;
+    pl.splitk_eff = std::min(pl.splitk, r.k_steps());
+    if (is_halo_tile(pl.tile)) pl.splitk_eff = std::min(pl.splitk_eff, r.channel_chunks());
+    pl.splitk_eff = std::max(pl.splitk_eff, 1);
+    pl.workspace_bytes = splitk_workspace_bytes(pl.splitk, r);
+}
+
+// can the split-K reduction of this launch apply the consumer's GroupNorm (pn_groups)?
+bool post_gn_fits(const madm_conv2d_args* a, int splitk_eff) {
+    if (splitk_eff <= 1 || a->pn_groups <= 0 || a->N <= 0 || a->N % a->pn_groups) return false;
+    if (a->epilogue != MADM_EPI_NONE || a->residual || a->stats || a->out_f32 || a->ln_colsum) return false;
+    return (a->N / a->pn_groups) % 2 == 0 && post_gn_lds(a->OH * a->OW, a->N, a->pn_groups) <= PGN_MAX_LDS;
+}
+
+int fill_params(const Request& r, IgemmP& p) {
+    const madm_conv2d_args* a = r.a;
     const int bke = (8 * madm_epc(a->dtype));
     MADM_REQUIRE(a->in1 && a->w && a->out, "conv2d: null tensor pointer");
     MADM_REQUIRE(a->C1 > 0 && a->C1 % bke == 0, "conv2d: C1=%d must be a positive multiple of %d", a->C1, bke);
@@ -1019,7 +1057,7 @@ int fill_params(const madm_conv2d_args* a, IgemmP& p) {
     p.B = a->B; p.IH = a->IH; p.IW = a->IW; p.OH = a->OH; p.OW = a->OW;
     p.KH = a->KH; p.KW = a->KW; p.stride = a->stride; p.pad_t = a->pad_t; p.pad_l = a->pad_l;
     p.upsample = a->upsample ? 1 : 0;
-    p.N = a->N; p.K = a->KH * a->KW * p.Ctot; p.M = a->B * a->OH * a->OW;
+    p.N = a->N; p.K = r.K; p.M = r.M;
     MADM_REQUIRE(!a->rowvec || (a->ldrv >= a->N && a->ldrv % 4 == 0), "conv2d: bad ldrv=%d", a->ldrv);
     p.ldr = a->ldr; p.ldo = a->ldo; p.ldrv = a->ldrv; p.epilogue = a->epilogue;
     p.ldw = a->ldw ? a->ldw : p.K;
@@ -1040,10 +1078,8 @@ int fill_params(const madm_conv2d_args* a, IgemmP& p) {
                      "conv2d: tensors must stay below 2 GiB (32-bit buffer offsets)");
         p.bytes1 = (unsigned)b1; p.bytes2 = (unsigned)b2; p.bytesw = (unsigned)bw;
     }
-    p.nk = p.K / bke;
-    p.splitk = a->splitk > p.nk ? p.nk : a->splitk;
-    if (p.splitk < 1) p.splitk = 1;
-    MADM_REQUIRE((long long)p.nk * (p.splitk + 1) < 0x7fffffffLL, "conv2d: K too large for the 32-bit slice arithmetic");
+    p.nk = r.k_steps();
+    MADM_REQUIRE((long long)p.nk * (std::min(a->splitk, p.nk) + 1) < 0x7fffffffLL, "conv2d: K too large for the 32-bit slice arithmetic");
     return MADM_OK;
 }
 
@@ -1058,23 +1094,21 @@ int launch_glds_v(const IgemmP& p, dim3 grid, hipStream_t s) {
 }
 
 template <typename T, int BM, int BN, int NS>
-int launch_glds(const IgemmP& p, dim3 grid, hipStream_t s) {
-    const bool lin = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && !p.upsample &&
-                     p.OH == p.IH && p.OW == p.IW;
+int launch_glds(const IgemmP& p, dim3 grid, hipStream_t s, bool lin) {
     return lin ? launch_glds_v<T, BM, BN, NS, true>(p, grid, s) : launch_glds_v<T, BM, BN, NS, false>(p, grid, s);
 }
 
 template <typename T>
 int launch(const IgemmP& p0, int t, hipStream_t s, const PostGn& pn) {
     IgemmP p = p0;
-    int bm, bn;
-    tile_dims(t, bm, bn);
+    const Tile& ti = *tile_info(t);
+    const int bm = ti.bm, bn = ti.bn;
     int rc;
-    if (t == 13) return launch_igemm_apanel<T>(p, s);
-    if (is_halo_tile(t)) {
-        rc = (t == 12) ? launch_conv3x3_h16<T>(p, bn, s)
-                       : ((t >= 9) ? launch_conv3x3_halo_dma<T>(p, bn, s) : launch_conv3x3_halo<T>(p, bn, s));
-    } else {
+    if (ti.family == APANEL) return launch_igemm_apanel<T>(p, s);
+    if (ti.family == H16) rc = launch_conv3x3_h16<T>(p, bn, s);
+    else if (ti.family == HALO_DMA) rc = launch_conv3x3_halo_dma<T>(p, bn, s);
+    else if (ti.family == HALO) rc = launch_conv3x3_halo<T>(p, bn, s);
+    else {   // IGEMM / GLDS: <BM, BN, slots> of the table row
         p.tilesN = (p.N + bn - 1) / bn;
         const int tilesM = (p.M + bm - 1) / bm;
         dim3 grid((unsigned)(tilesM * p.tilesN), 1, (unsigned)p.splitk);
@@ -1084,16 +1118,13 @@ int launch(const IgemmP& p0, int t, hipStream_t s, const PostGn& pn) {
         else if (t == 2 && lin) igemm_kernel<T, 128, 64, 3, true><<<grid, 256, 0, s>>>(p);
         else if (t == 2) igemm_kernel<T, 128, 64, 3, false><<<grid, 256, 0, s>>>(p);
         else if (t == 6) igemm_kernel<T, 64, 64, 8, false><<<grid, 256, 0, s>>>(p);
-        else if (t == 7) { if (int e = launch_glds<T, 64, 64, 4>(p, grid, s)) return e; }
-        else if (t == 8) { if (int e = launch_glds<T, 128, 64, 3>(p, grid, s)) return e; }
-        else if (t == 11) { if (int e = launch_glds<T, 64, 64, 3>(p, grid, s)) return e; }
-        else if (t == 14) { if (int e = launch_glds<T, 128, 128, 3>(p, grid, s)) return e; }
-        else if (t == 15) { if (int e = launch_glds<T, 128, 128, 2>(p, grid, s)) return e; }
-        // two-slot rings of the small tiles: 32 / 48 KB rings + the 3 KB constant stash = 35 / 51 KB of LDS: four / three blocks
-        // per CU by LDS (short-K layers: the blocks' prologues and epilogues cover each other instead of a deep ring covering
-        // the K loop)
-        else if (t == 16) { if (int e = launch_glds<T, 64, 64, 2>(p, grid, s)) return e; }
-        else if (t == 17) { if (int e = launch_glds<T, 128, 64, 2>(p, grid, s)) return e; }
+        else if (t == 7) { if (int e = launch_glds<T, 64, 64, 4>(p, grid, s, lin)) return e; }
+        else if (t == 8) { if (int e = launch_glds<T, 128, 64, 3>(p, grid, s, lin)) return e; }
+        else if (t == 11) { if (int e = launch_glds<T, 64, 64, 3>(p, grid, s, lin)) return e; }
+        else if (t == 14) { if (int e = launch_glds<T, 128, 128, 3>(p, grid, s, lin)) return e; }
+        else if (t == 15) { if (int e = launch_glds<T, 128, 128, 2>(p, grid, s, lin)) return e; }
+        else if (t == 16) { if (int e = launch_glds<T, 64, 64, 2>(p, grid, s, lin)) return e; }
+        else if (t == 17) { if (int e = launch_glds<T, 128, 64, 2>(p, grid, s, lin)) return e; }
         else if (lin) igemm_kernel<T, 64, 64, 4, true><<<grid, 256, 0, s>>>(p);
         else igemm_kernel<T, 64, 64, 4, false><<<grid, 256, 0, s>>>(p);
         rc = madm_check_launch("igemm_kernel");
@@ -1146,55 +1177,46 @@ int madm_set_tuning_profile(int profile) {
 }
 int madm_get_tuning_profile(void) { return g_tuning_profile.load(std::memory_order_relaxed); }
 
-size_t madm_conv2d_workspace_bytes(const madm_conv2d_args* a) {
-    if (!a || a->splitk <= 1) return 0;
-    const size_t M = (size_t)a->B * a->OH * a->OW;
-    return (size_t)a->splitk * M * (size_t)a->N * sizeof(float);
-}
+const char* madm_conv2d_tile_name(int tile) { return tile_info(tile) ? tile_info(tile)->name : nullptr; }
 
-int madm_conv2d_pick_tile(const madm_conv2d_args* a) {
-    if (!a) return 0;
-    return pick_tile(a);
-}
-
-int madm_conv2d_has_tuned_row(const madm_conv2d_args* a) {
-    if (!a || !madm_dtype_ok(a->dtype)) return 0;
-    const int M = a->B * a->OH * a->OW, K = a->KH * a->KW * (a->C1 + a->C2);
-    if (h16_upsample_eligible(a) && find_tuned(a->dtype, M, a->N, K, a->KH, 2)) return 1;
-    return find_tuned(a->dtype, M, a->N, K, a->KH, variant_of(a)) ? 1 : 0;
-}
-
-int madm_conv2d_suggest_splitk(const madm_conv2d_args* a) {
-    if (!a) return 1;
-    const int bke = (8 * madm_epc(a->dtype));
-    const int M = a->B * a->OH * a->OW;
-    const int Ktot = a->KH * a->KW * (a->C1 + a->C2);
-    const int nk = Ktot / bke;
-    const int chosen = pick_tile(a);
-    if (const Tuned* t = find_tuned(a->dtype, M, a->N, Ktot, a->KH, variant_of(a)))
-        if (t->tile == chosen) return t->splitk;
-    int bm, bn;
-    tile_dims(pick_tile(a), bm, bn);
-    const long long tiles = (long long)((M + bm - 1) / bm) * ((a->N + bn - 1) / bn);
-    if (tiles >= 192 || nk < 8) return 1;
-    long long s = (512 + tiles - 1) / tiles;
-    if (s > nk / 4) s = nk / 4;
-    if (s > 32) s = 32;
-    if (s < 1) s = 1;
-    return (int)s;
+// A caller used to decide in stages, each on what the earlier ones had filled in (apanel_eligible looks at splitk and stats): split-K
+// suggested for the tile picked WITHOUT split-K and statistics, the post-GroupNorm asked with the split-K set and still no statistics,
+// the launch picked with everything set.  The same stages run here, on one copy of the request and one reading of the process state.
+int madm_conv2d_make_plan(const madm_conv2d_args* request, madm_conv2d_plan* plan) {
+    MADM_REQUIRE(request != nullptr && plan != nullptr, "conv2d plan: null argument");
+    MADM_REQUIRE(madm_dtype_ok(request->dtype), "conv2d plan: bad dtype %d", request->dtype);
+    MADM_REQUIRE(request->splitk >= 0, "conv2d plan: splitk must be 0 (the library chooses) or >= 1");
+    madm_conv2d_args c = *request;
+    const Request r(&c);
+    c.stats = nullptr; c.pn_gamma = nullptr;
+    if (request->splitk == 0) {
+        c.splitk = 1;
+        c.splitk = std::max(1, suggest_splitk(r));
+    }
+    resolve(r, *plan);
+    plan->post_gn = post_gn_fits(&c, plan->splitk_eff) ? 1 : 0;
+    if (!plan->post_gn && request->stats) {   // the statistics come from the conv's own epilogue
+        c.stats = request->stats;
+        resolve(r, *plan);
+    }
+    // a row was FOUND for the shape: the stride-2 -> plain fallback and the upsample lookup count
+    plan->tuned_row = ((h16_upsample_eligible(&c) && r.row(2)) || r.row(variant_of(&c))) ? 1 : 0;
+    return MADM_OK;
 }
 
 int madm_conv2d_fwd(const madm_conv2d_args* a, void* stream) {
+    MADM_REQUIRE(a != nullptr, "conv2d: null args");
+    MADM_REQUIRE(madm_dtype_ok(a->dtype), "conv2d: bad dtype %d", a->dtype);
+    const Request r(a);
     IgemmP p;
-    int rc = fill_params(a, p);
+    int rc = fill_params(r, p);
     if (rc) return rc;
-    if (p.splitk > 1) {
-        const size_t need = (size_t)p.splitk * p.M * (size_t)p.N * sizeof(float);
-        MADM_REQUIRE(a->workspace && a->workspace_bytes >= need,
-                     "conv2d: split-K %d needs %zu workspace bytes, got %zu", p.splitk, need,
-                     a->workspace_bytes);
-    }
-    const int t = pick_tile(a);
+    madm_conv2d_plan pl;
+    resolve(r, pl);
+    p.splitk = pl.splitk_eff;
+    const size_t need = splitk_workspace_bytes(p.splitk, r);
+    MADM_REQUIRE(!need || (a->workspace && a->workspace_bytes >= need),
+                 "conv2d: split-K %d needs %zu workspace bytes, got %zu", p.splitk, need, a->workspace_bytes);
     if (a->gn_sums1) {
         MADM_REQUIRE(halo_eligible(a),
                      "conv2d: fused GroupNorm needs a 3x3 / stride-1 / pad-1 conv on a map of at least 8x16 "
@@ -1211,37 +1233,19 @@ int madm_conv2d_fwd(const madm_conv2d_args* a, void* stream) {
         p.gn_sums1 = a->gn_sums1; p.gn_sums2 = a->gn_sums2; p.gn_gamma = a->gn_gamma; p.gn_beta = a->gn_beta;
         p.gn_G = a->gn_groups; p.gn_eps = a->gn_eps; p.gn_magic = magic; p.act = a->gn_act;
     }
-    if (is_halo_tile(t)) {   // the halo kernel splits K by whole channel chunks
-        const int nchunks = p.Ctot / ((8 * madm_epc(a->dtype)));
-        if (p.splitk > nchunks) p.splitk = nchunks;
-    }
     PostGn pn{nullptr, nullptr, 0, 0.f, 0};
     if (a->pn_gamma) {
-        MADM_REQUIRE(madm_conv2d_can_post_groupnorm(a),
+        MADM_REQUIRE(post_gn_fits(a, p.splitk),
                      "conv2d: the GroupNorm of the output rides on the split-K reduction: effective splitk > 1, plain "
                      "epilogue, no residual / stats / out_f32, even N / groups, HW * N / groups * 4 <= %zu bytes of LDS "
-                     "(madm_conv2d_can_post_groupnorm tells)", PGN_MAX_LDS);
+                     "(madm_conv2d_make_plan tells)", PGN_MAX_LDS);
         MADM_REQUIRE(a->pn_beta && a->pn_eps > 0.f && a->pn_act >= 0 && a->pn_act <= 2, "conv2d: bad pn_beta / pn_eps / pn_act");
         pn = PostGn{a->pn_gamma, a->pn_beta, a->pn_groups, a->pn_eps, a->pn_act};
     }
     hipStream_t s = (hipStream_t)stream;
-    if (a->dtype == MADM_F32) return launch<float>(p, t, s, pn);
-    if (a->dtype == MADM_F16) return launch<f16_t>(p, t, s, pn);
-    return launch<bf16_t>(p, t, s, pn);
-}
-
-int madm_conv2d_can_post_groupnorm(const madm_conv2d_args* a) {
-    if (!a || !madm_dtype_ok(a->dtype) || a->splitk <= 1 || a->pn_groups <= 0 || a->N <= 0 || a->N % a->pn_groups) return 0;
-    if (a->epilogue != MADM_EPI_NONE || a->residual || a->stats || a->out_f32 || a->ln_colsum) return 0;
-    const int bke = 8 * madm_epc(a->dtype);
-    const int Ctot = a->C1 + a->C2;
-    int sk = a->splitk;                                   // the clamps of fill_params / madm_conv2d_fwd
-    const int nk = a->KH * a->KW * Ctot / bke;
-    if (sk > nk) sk = nk;
-    if (is_halo_tile(pick_tile(a)) && sk > Ctot / bke) sk = Ctot / bke;
-    if (sk <= 1) return 0;
-    const int cpg = a->N / a->pn_groups;
-    return (cpg % 2 == 0 && post_gn_lds(a->OH * a->OW, a->N, a->pn_groups) <= PGN_MAX_LDS) ? 1 : 0;
+    if (a->dtype == MADM_F32) return launch<float>(p, pl.tile, s, pn);
+    if (a->dtype == MADM_F16) return launch<f16_t>(p, pl.tile, s, pn);
+    return launch<bf16_t>(p, pl.tile, s, pn);
 }
 
 int madm_conv2d_can_fuse_groupnorm(const madm_conv2d_args* a) { return a && halo_eligible(a) ? 1 : 0; }

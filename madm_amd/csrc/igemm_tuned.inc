@@ -1,4 +1,4 @@
-// {dtype (0 f32, 1 bf16), M, N, K, KH, variant (0 plain, 1 GroupNorm-fused, 2 upsample), tile (1=128x128, 2=128x64, 3=64x64 igemm; 13 = A-stationary linear kernel igemm_apanel.hip; 4 / 5 = halo conv3x3 x128 / x64; 6 = 64x64 igemm, 8-deep prefetch; 7 / 8 / 11 = LDS-DMA igemm 64x64 / 128x64 / 64x64 short ring; 9 / 10 = LDS-DMA halo x128 / x64), splitk}
+// {dtype (0 f32, 1 bf16), M, N, K, KH, variant (0 plain, 1 GroupNorm-fused, 2 upsample, 3 stride 2), tile (1..17: the table g_tiles of igemm.hip), splitk}
 // measured by tools/tune_insitu.py on MI355X (whole eager forwards, cold weights), bf16, round 1; plain and
 // GroupNorm-fused variants come from runs under different fusion policies (MADM_FUSE_GN_MAX_N)
 // -- feature extractor, bs=2, 512x512 (BASELINE configs[1])

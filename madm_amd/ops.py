@@ -6,11 +6,12 @@ channels-last 2-D tensors ``[B*H*W, C]``.  There is no fallback path.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 from . import _debug, _lib
-from ._lib import (lib, check, Conv2dArgs, AttentionArgs, EPI_NONE, EPI_GEGLU, EPI_RELU, MADM_F32, MADM_BF16, MADM_F16,
+from ._lib import (lib, check, Conv2dArgs, Conv2dPlan, AttentionArgs, EPI_NONE, EPI_GEGLU, EPI_RELU, MADM_F32, MADM_BF16, MADM_F16,
                    ACT_NONE, ACT_SILU, ACT_RELU)
 
 _DT = {torch.float32: MADM_F32, torch.bfloat16: MADM_BF16, torch.float16: MADM_F16}
@@ -134,43 +135,37 @@ PROFILE = None
 # cancelled -- no overhead estimate to subtract (bench.py's roofline; the pass's results are thrown away: fused
 # statistics are accumulated three times).
 PROFILE_DIFF = False
-_TILE_NAMES = {1: "igemm_128x128", 2: "igemm_128x64", 3: "igemm_64x64", 4: "conv3x3_halo_x128", 5: "conv3x3_halo_x64",
-               6: "igemm_64x64d", 7: "igemm_glds_64x64", 8: "igemm_glds_128x64", 9: "conv3x3_halo_dma_x128",
-               10: "conv3x3_halo_dma_x64", 11: "igemm_glds_64x64s", 12: "conv3x3_h16_x128", 13: "igemm_apanel",
-               14: "igemm_glds_128x128", 15: "igemm_glds_128x128d",
-               16: "igemm_glds_64x64d", 17: "igemm_glds_128x64d"}
-EXP_NO_STATS = bool(int(__import__('os').environ.get('MADM_EXP_NO_STATS', '0')))   # timing experiment only
-FORCE_SPLITK = None   # tools/tune_insitu.py: split-K factor forced on every small-M launch
-if os.environ.get("MADM_EXP_SPLITK"):   # experiment: e.g. 1 = no split-K anywhere (does the staged pipeline still want it?)
-    FORCE_SPLITK = int(os.environ["MADM_EXP_SPLITK"])
+EXP_NO_STATS = bool(int(os.environ.get('MADM_EXP_NO_STATS', '0')))   # timing experiment only
+# tools/tune_insitu.py: split-K factor forced on every small-M launch (env MADM_EXP_SPLITK: e.g. 1 = no split-K anywhere)
+FORCE_SPLITK = int(os.environ["MADM_EXP_SPLITK"]) if os.environ.get("MADM_EXP_SPLITK") else None
 # timing experiments only (results become garbage): launches of the named classes are skipped -- "layernorm", "gn_apply",
-# "attention", "softmax", or tile codes of madm_conv2d_pick_tile ("tile7", ...): what would the step cost without them?
+# "attention", "softmax", or tile codes of madm_conv2d_plan ("tile7", ...): what would the step cost without them?
 EXP_SKIP = set(filter(None, os.environ.get("MADM_EXP_SKIP", "").split(",")))
-_SKIP_RE = [__import__("re").compile(t[3:]) for t in EXP_SKIP if t.startswith("re:")]
+_SKIP_RE = [re.compile(t[3:]) for t in EXP_SKIP if t.startswith("re:")]
 
 
 def _skip_match(desc):
     return any(r.search(desc) for r in _SKIP_RE)
 
 
-# When TILE_LOG is a list, every forward conv / linear launch appends (description, tile code, split-K, has_tuned_row, FLOPs):
+# When TILE_LOG is a list, every forward conv / linear launch appends (description, tile code, split-K, plan.tuned_row, FLOPs):
 # tests/test_parity_gpu.py::test_bench_workloads_have_tuned_rows
 TILE_LOG = None
 FUSE_GN = True   # fold GroupNorm(+SiLU) into eligible 3x3 convs (debug switch)
 # the GroupNorm that consumes a split-K conv rides on its reduction (conv2d(post_gn=...)); env MADM_NO_POST_GN for A/B runs
 POST_GN = not bool(int(os.environ.get("MADM_NO_POST_GN", "0")))
-HALO_MIN_W = int(__import__("os").environ.get("MADM_HALO_MIN_W", "8"))   # mirrors halo_min_width() of igemm.hip
-import os as _os
-FUSE_GN_MAX_N = int(_os.environ.get("MADM_FUSE_GN_MAX_N", "256"))   # ... whose output has at most 256 channels: the
+FUSE_GN_MAX_N = int(os.environ.get("MADM_FUSE_GN_MAX_N", "256"))   # ... whose output has at most 256 channels: the
 # transform is redone once per output-channel tile, so on the wide UNet layers (320 .. 1280 channels, 5 .. 20 tiles of 64) a
 # stand-alone GroupNorm pass + the plain conv is less total work.  Same-box A/B with both variants tuned (images/s,
 # overlapped / serial): 128 -> 269 / 220, 256 -> 270 / 220, unlimited -> 262 / 221.  Env override for A/B runs.
 
 
 def can_fuse_groupnorm(IH, IW, KH, stride, pad, asym_pad, upsample):
-    """Mirror of madm_conv2d_can_fuse_groupnorm (the LDS halo-tile 3x3 kernel applies)."""
-    return (FUSE_GN and KH == 3 and stride == 1 and pad == 1 and not asym_pad and not upsample and IH >= 8
-            and IW >= HALO_MIN_W)
+    """madm_conv2d_can_fuse_groupnorm (the LDS halo-tile 3x3 kernel applies) for a conv of nn.Conv2d's description."""
+    pad = 0 if asym_pad else pad
+    a = Conv2dArgs(KH=KH, KW=KH, stride=stride, pad_t=pad, pad_l=pad, upsample=int(bool(upsample)), IH=IH, IW=IW,
+                   OH=IH, OW=IW)   # the size a conv the kernel takes (3x3, stride 1, pad 1, no upsample) keeps
+    return FUSE_GN and bool(lib.madm_conv2d_can_fuse_groupnorm(ctypes.byref(a)))
 
 
 def groupnorm_finalize(stats, B, HW, G, gamma, beta, eps):
@@ -288,50 +283,48 @@ def conv2d(x1, w, B, IH, IW, *, N, x2=None, KH=1, KW=1, stride=1, pad_t=0, pad_l
         assert cs.dtype == torch.float32 and cs.is_contiguous() and cs.numel() == N and x2 is None and KH == 1 and gn is None
         a.ln_colsum, a.ln_eps = cs.data_ptr(), float(eps)
         splitk = 1       # every workgroup must walk whole rows (the row sums come from its own A fragments)
-    a.splitk = 1
     if FORCE_SPLITK is not None and splitk is None:
         nk = KH * KW * (C1 + C2) // k_tile(x1.dtype)
         splitk = FORCE_SPLITK if (M <= 16384 and FORCE_SPLITK <= max(1, nk // 2)) else 1
-    if splitk is None:
-        splitk = lib.madm_conv2d_suggest_splitk(ctypes.byref(a))
-    a.splitk = max(1, int(splitk))
-    applied = False
+    # the request: splitk 0 = the library chooses, pn_groups = carry the consumer's norm if the launch can, stats = wanted otherwise
+    a.splitk = 0 if splitk is None else max(1, int(splitk))
     if post_gn is not None:
         gamma, beta, groups, eps, act = post_gn
         _need_cuda(gamma, beta)
         assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.is_contiguous() and beta.is_contiguous()
         assert gamma.numel() == N and beta.numel() == N and residual is None and ln is None
-        a.pn_groups = int(groups)
-        if POST_GN and lib.madm_conv2d_can_post_groupnorm(ctypes.byref(a)):
-            a.pn_gamma, a.pn_beta, a.pn_eps, a.pn_act = gamma.data_ptr(), beta.data_ptr(), float(eps), _act_code(act=act)
-            applied = True
-    if stats is not None and not applied:
+        a.pn_groups = int(groups) if POST_GN else 0
+    if stats is not None:
         assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == B * N * 2
         a.stats = stats.data_ptr()
-    ws = None
-    if a.splitk > 1:
-        nbytes = lib.madm_conv2d_workspace_bytes(ctypes.byref(a))
-        ws = _workspace(nbytes, x1.device)
-        a.workspace = ws.data_ptr()
-        a.workspace_bytes = ws.numel()
+    plan = Conv2dPlan()
+    check(lib.madm_conv2d_make_plan(ctypes.byref(a), ctypes.byref(plan)), "madm_conv2d_make_plan")
+    a.splitk = plan.splitk
+    applied = bool(plan.post_gn)
+    if applied:
+        a.stats = None
+        a.pn_gamma, a.pn_beta, a.pn_eps, a.pn_act = gamma.data_ptr(), beta.data_ptr(), float(eps), _act_code(act=act)
+    if plan.workspace_bytes:
+        ws = _workspace(plan.workspace_bytes, x1.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
     if EXP_SKIP:
         # timing experiments only (tools/exp/skip_sensitivity.sh): "tileN", or "re:<regex>" on "k<KH> s<stride> M.. N.. K.."
-        if ("tile%d" % lib.madm_conv2d_pick_tile(ctypes.byref(a))) in EXP_SKIP or _skip_match(
+        if ("tile%d" % plan.tile) in EXP_SKIP or _skip_match(
                 f"k{KH} s{stride}{' up' if upsample else ''} M{M} N{N} K{KH * KW * (C1 + C2)}"):
             return out if post_gn is None else (out, applied)
     if TILE_LOG is not None:
         TILE_LOG.append((f"dt{a.dtype} M{M} N{N} K{KH * KW * (C1 + C2)} k{KH} s{stride}{' up' if upsample else ''}"
-                         f"{' gn' if gn is not None else ''}", lib.madm_conv2d_pick_tile(ctypes.byref(a)), a.splitk,
-                         bool(lib.madm_conv2d_has_tuned_row(ctypes.byref(a))), 2.0 * M * N * KH * KW * (C1 + C2)))
+                         f"{' gn' if gn is not None else ''}", plan.tile, plan.splitk, bool(plan.tuned_row),
+                         2.0 * M * N * KH * KW * (C1 + C2)))
     if PROFILE is None:
         check(lib.madm_conv2d_fwd(ctypes.byref(a), _stream()), "madm_conv2d_fwd")
     else:
         an, ak = alg_nk if alg_nk is not None else (N, KH * KW * (C1 + C2))
-        name = _TILE_NAMES[lib.madm_conv2d_pick_tile(ctypes.byref(a))] + _SUFFIX[x1.dtype]
+        name = lib.madm_conv2d_tile_name(plan.tile).decode() + _SUFFIX[x1.dtype]
         desc = (f"M{M} N{N} K{KH * KW * (C1 + C2)} k{KH} s{stride}{' up' if upsample else ''}"
                 f"{' gn' if gn is not None else ''}{' ln' if ln is not None else ''}"
                 f"{' geglu' if epilogue == EPI_GEGLU else ''}{' res' if residual is not None else ''}"
-                f" sk{a.splitk}{' +gn' if applied else ''}")
+                f" sk{plan.splitk}{' +gn' if applied else ''}")
         es = x1.element_size()
         # algorithmic HBM bytes: every input element, weight and output element once
         nbytes = (B * IH * IW * (C1 + C2) * es + w.numel() * es

@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    assert _lib.lib.madm_abi_version() == 5
+    assert _lib.lib.madm_abi_version() == 6
 
 
 def test_struct_layout_matches_header_field_order():
@@ -85,6 +85,7 @@ def test_gradient_struct_layouts_match_header():
     assert _header_struct_fields("madm_conv2d_wgrad_args") == [f[0] for f in _lib.Conv2dWgradArgs._fields_]
     assert _header_struct_fields("madm_attention_bwd_args") == [f[0] for f in _lib.AttentionBwdArgs._fields_]
     assert _header_struct_fields("madm_attention_args") == [f[0] for f in _lib.AttentionArgs._fields_]
+    assert _header_struct_fields("madm_conv2d_plan") == [f[0] for f in _lib.Conv2dPlan._fields_]
 
 
 def test_gradient_entry_points_validate_arguments_without_gpu():
@@ -183,12 +184,21 @@ def test_pack_entry_points_validate_arguments_without_gpu():
     assert lib.madm_pack_weight(1, p, p, 32, 4, 8, 1, 1, one, 64, 0, None) == -1 and b"ldo" in lib.madm_last_error()
     assert lib.madm_pack_weight(1, p, p, 64, 3, 8, 1, 1, one, 64, 1, None) == -1 and b"even row count" in lib.madm_last_error()
     assert lib.madm_fold_layernorm_pack(1, p, None, None, p, p, p, p, 4, 64, 0, None) == -1
-    a = __import__("madm_amd._lib", fromlist=["Conv2dArgs"]).Conv2dArgs()
-    assert lib.madm_conv2d_can_post_groupnorm(ctypes.byref(a)) == 0          # no split-K, no groups: cannot carry the norm
+    _lib = __import__("madm_amd._lib", fromlist=["Conv2dArgs"])
+    a, plan = _lib.Conv2dArgs(), _lib.Conv2dPlan()
+
+    def can_post_groupnorm():
+        assert lib.madm_conv2d_make_plan(ctypes.byref(a), ctypes.byref(plan)) == 0
+        return plan.post_gn
+
+    assert can_post_groupnorm() == 0          # no split-K, no groups: cannot carry the norm
     a.dtype, a.splitk, a.pn_groups, a.N, a.C1, a.KH, a.KW, a.OH, a.OW, a.IH, a.IW, a.B = 1, 4, 32, 1280, 512, 1, 1, 16, 16, 16, 16, 2
-    assert lib.madm_conv2d_can_post_groupnorm(ctypes.byref(a)) == 1          # 16 x 16 x 40 channels x 4 B = 40 KB of LDS
+    assert can_post_groupnorm() == 1          # 16 x 16 x 40 channels x 4 B = 40 KB of LDS
+    assert (plan.splitk, plan.splitk_eff, plan.workspace_bytes) == (4, 4, 4 * 512 * 1280 * 4)
     a.OH = a.OW = a.IH = a.IW = 64
-    assert lib.madm_conv2d_can_post_groupnorm(ctypes.byref(a)) == 0          # 640 KB: the group does not fit
+    assert can_post_groupnorm() == 0          # 640 KB: the group does not fit
+    a.splitk = -1
+    assert lib.madm_conv2d_make_plan(ctypes.byref(a), ctypes.byref(plan)) == -1 and b"splitk" in lib.madm_last_error()
     assert lib.madm_groupnorm_apply_cat(1, p, p, p, 64, 1, 1, 32, 32, 32, None, p, p, p, 1e-5, 0, None) == -1
 
 
@@ -398,11 +408,11 @@ def test_tuned_table_rows_are_valid_and_unique():
 def test_tuning_profiles_switch_rows_and_pin():
     """Round 6: madm_set_tuning_profile(1) puts the lone-launch rows of igemm_tuned_latency.inc in front of the throughput
     table; ops.tuning_profile restores the previous profile on exit, and a pinned context (the graph runners: "throughput") makes the
-    sync_profile() of a synchronous forward inside it a no-op.  Host-side only: pick_tile / suggest_splitk need no GPU."""
+    sync_profile() of a synchronous forward inside it a no-op.  Host-side only: madm_conv2d_make_plan needs no GPU."""
     import ctypes
     import re
     from madm_amd import ops
-    from madm_amd._lib import lib, Conv2dArgs, MADM_F16
+    from madm_amd._lib import lib, Conv2dArgs, Conv2dPlan, MADM_F16
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "madm_amd", "csrc")
 
     def rows(name):
@@ -423,9 +433,14 @@ def test_tuning_profiles_switch_rows_and_pin():
     a = Conv2dArgs()
     a.dtype, a.C1, a.C2, a.B, a.IH, a.IW, a.OH, a.OW = MADM_F16, K, 0, 1, M, 1, M, 1
     a.KH = a.KW = a.stride = 1
-    a.N, a.splitk = N, 1
+    a.N, a.splitk = N, 0                                            # split-K: the library chooses
     a.in1 = a.w = a.out = 1
-    pick = lambda: (lib.madm_conv2d_pick_tile(ctypes.byref(a)), lib.madm_conv2d_suggest_splitk(ctypes.byref(a)))
+    plan = Conv2dPlan()
+
+    def pick():
+        assert lib.madm_conv2d_make_plan(ctypes.byref(a), ctypes.byref(plan)) == 0
+        return plan.tile, plan.splitk
+
     assert lib.madm_get_tuning_profile() == 0 and pick() == base[key]
     with ops.tuning_profile("latency"):
         assert lib.madm_get_tuning_profile() == 1 and pick() == lat[key]
@@ -464,3 +479,77 @@ def test_stream_safe_cache_and_side_build_hooks_are_inert_on_the_host():
     before = ops.SIDE_BUILDS_NOTED
     ops.note_build()                                    # no side_builds context: nothing happens, no CUDA call
     assert ops.SIDE_BUILDS_NOTED == before and ops._SIDE_BUILD_MAIN is None
+
+
+_TILE_NAMES = {1: "igemm_128x128", 2: "igemm_128x64", 3: "igemm_64x64", 4: "conv3x3_halo_x128", 5: "conv3x3_halo_x64",
+               6: "igemm_64x64d", 7: "igemm_glds_64x64", 8: "igemm_glds_128x64", 9: "conv3x3_halo_dma_x128",
+               10: "conv3x3_halo_dma_x64", 11: "igemm_glds_64x64s", 12: "conv3x3_h16_x128", 13: "igemm_apanel",
+               14: "igemm_glds_128x128", 15: "igemm_glds_128x128d",
+               16: "igemm_glds_64x64d", 17: "igemm_glds_128x64d"}
+
+
+def test_tile_names_are_the_kernel_classes_bench_keys_on():
+    """bench.py keys its ``kernels`` / ``roofline.layers`` output on these names (+ the dtype suffix): the dict ops.py held up to ABI 5."""
+    from madm_amd._lib import lib
+    assert {t: lib.madm_conv2d_tile_name(t).decode() for t in range(1, 18)} == _TILE_NAMES
+    assert lib.madm_conv2d_tile_name(0) is None and lib.madm_conv2d_tile_name(18) is None and lib.madm_conv2d_tile_name(-1) is None
+
+
+def test_can_fuse_groupnorm_asks_the_library_and_keeps_its_rule():
+    """ops.can_fuse_groupnorm asks madm_conv2d_can_fuse_groupnorm; the rule it restated in Python up to ABI 5 stays here as the reference."""
+    from madm_amd import ops
+    assert "MADM_HALO_MIN_W" not in os.environ and ops.FUSE_GN
+    n = 0
+    for IH in range(4, 33):
+        for IW in range(4, 33):
+            for KH in (1, 3):
+                for stride in (1, 2):
+                    for pad in (0, 1):
+                        for asym_pad in (False, True):
+                            for upsample in (False, True):
+                                want = (KH == 3 and stride == 1 and pad == 1 and not asym_pad and not upsample and IH >= 8
+                                        and IW >= 8)
+                                assert ops.can_fuse_groupnorm(IH, IW, KH, stride, pad, asym_pad, upsample) == want, \
+                                    (IH, IW, KH, stride, pad, asym_pad, upsample)
+                                n += want
+    assert n == 25 * 25
+    ops.FUSE_GN = False
+    try:
+        assert not ops.can_fuse_groupnorm(16, 16, 3, 1, 1, False, False)
+    finally:
+        ops.FUSE_GN = True
+
+
+def _conv_plan_fixture():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("conv_plan_fixture", os.path.join(ROOT, "tools", "conv_plan_fixture.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    return tool
+
+
+def test_conv_plans_replay_the_recorded_decisions():
+    """Differential replay (tools/conv_plan_fixture.py): tests/golden/conv_plans.json was recorded from the last ABI-5 build through
+    the staged queries ops.conv2d made then (suggest_splitk -> can_post_groupnorm -> workspace_bytes / pick_tile / has_tuned_row);
+    madm_conv2d_make_plan must give the same (tile, split-K, post-GN carried, workspace bytes, row found) for every request of the
+    grid: the explicit cases one by one (a mismatch names its request), the whole grid by the SHA-256 of its outcomes.  A change
+    that moves a launch it did not mean to move fails here; one that means to regenerates the fixture and shows the moved cases."""
+    import json
+    from madm_amd import _lib
+    tool = _conv_plan_fixture()
+    assert [f[0] for f in tool.Args._fields_] == [f[0] for f in _lib.Conv2dArgs._fields_]
+    assert ctypes.sizeof(tool.Args) == ctypes.sizeof(_lib.Conv2dArgs)
+    assert tool.Plan._fields_ == _lib.Conv2dPlan._fields_
+    for env in ("MADM_TUNED_FILE", "MADM_HALO_MIN_W", "MADM_NO_H16"):
+        assert env not in os.environ, env
+    want = json.load(open(tool.FIXTURE))
+    assert len(want["explicit"]) >= 200 and all(len(c) == len(want["fields"]) for c in want["explicit"])
+    lib = tool.open_lib(_lib.LIB_PATH, "new")
+    for case in want["explicit"]:
+        assert tool.run_case(lib, "new", case) == case[22:], dict(zip(want["fields"], case))
+    n, sha, explicit, tiles, seen = tool.run_grid(lib, "new")
+    assert explicit == want["explicit"]
+    assert (n, sha) == (want["cases"], want["sha256"])
+    # the grid reaches every tile code and both outcomes of every boolean
+    assert tiles == set(range(1, 18)) and all(s == {0, 1} for s in seen), (tiles, seen)
+    assert lib.madm_get_tuning_profile() == 0

@@ -543,7 +543,7 @@ def test_bench_workloads_have_tuned_rows(cuda):
     """VERDICT r5 #7 / DESIGN 12.3: the eval forward ran 2 x too long on two B = 1 shapes for a whole round because the launches
     had silently left the tuned table.  Every forward conv / linear launch of the bench workloads at their shipped sizes --
     extract (configs[1], f16 and bf16 share the rows), extract + one r = 8 adapter, eval (configs[2]), sliding windows
-    (configs[4] geometry) -- must be decided by a ROW of madm_amd/csrc/igemm_tuned.inc (madm_conv2d_has_tuned_row), not by the
+    (configs[4] geometry) -- must be decided by a ROW of madm_amd/csrc/igemm_tuned.inc (madm_conv2d_plan.tuned_row), not by the
     fall-through heuristics; the message lists the missing rows in the table's own format (pinned to today's choice) so
     that a kernel change that moves shapes is followed by a re-tune (tools/tune_concurrent.py) or an explicit row."""
     import bench
