@@ -488,6 +488,15 @@ int madm_adamw_step(float* p, const float* g, float* m, float* v, size_t n, floa
 int madm_adamw_step_table(float* p, const float* g, float* m, float* v, size_t n, const int* chunk_tensor, const float* hyper,
                           float beta1, float beta2, float eps, float grad_scale, void* stream);
 int madm_ema_update(float* ema, const float* p, size_t n, float alpha, void* stream);
+/* Checkpoint snapshot (no reference counterpart; additive to ABI 6): copies src to dst and, in the same read, ADDS the
+ * buffer's 64-bit fingerprint into *fingerprint (the caller zeroes it).  Element i with the 32-bit pattern w (the bit
+ * pattern, not the value) contributes, modulo 2^64,
+ *     x = ((index_base + i) << 32) | w;  h = x * 0x9E3779B97F4A7C15;  h ^= h >> 32;  h *= 0xD6E8FEB86659FD93;  h ^= h >> 32
+ * -- an integer sum: the same value in every run and launch geometry, and the fingerprint of a buffer is the sum of the
+ * fingerprints of its pieces (with their index_base).  dst == NULL: fingerprint only; fingerprint == NULL: copy only.
+ * Refused (-1, no launch): null src, both outputs null, n == 0, src / dst not 16-byte aligned, index_base + n > 2^32. */
+int madm_snapshot_f32(const float* src, float* dst, size_t n, unsigned long long index_base, unsigned long long* fingerprint,
+                      void* stream);
 
 /* ---- label / pseudo-label pipeline of the self-training step, on the device (bit-exact index work) --------------
  * MTMADISE.convert_label_to_rgb (modeling/meta_arch/mtmadise.py:159-175: label.cpu() -> PIL 'P' image ->

@@ -4,7 +4,9 @@
 //   madm_adamw_step    -- torch.optim.AdamW step (config_files/common/optim.py:8-17) with the GradScaler unscale and
 //                         the clip coefficient folded in as one gradient scale
 //   madm_ema_update    -- teacher EMA (modeling/meta_arch/cmdise.py:337-349)
-// 16-byte accesses per lane, grid-stride; algorithmic traffic 28 / 12 / 4 bytes per element.
+//   madm_snapshot_f32  -- checkpoint snapshot: copy into a staging buffer and, in the same read, the buffer's 64-bit
+//                         position-dependent fingerprint (an integer sum: the same value in any launch geometry)
+// 16-byte accesses per lane, grid-stride; algorithmic traffic 28 / 12 / 4 / 8 bytes per element.
 #include "common.hpp"
 
 namespace {
@@ -94,6 +96,45 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const
         for (size_t i = n4 * 4; i < n; ++i) ema[i] = alpha * ema[i] + b * p[i];
 }
 
+// fingerprint of one element: a 64-bit mix of (global index, bit pattern); all arithmetic modulo 2^64
+__device__ __forceinline__ unsigned long long fp_mix(unsigned long long index, float value) {
+    unsigned long long h = (index << 32) | (unsigned long long)__float_as_uint(value);
+    h *= 0x9E3779B97F4A7C15ull;
+    h ^= h >> 32;
+    h *= 0xD6E8FEB86659FD93ull;
+    h ^= h >> 32;
+    return h;
+}
+
+template <bool COPY, bool FP>
+__global__ __launch_bounds__(256) void snapshot_kernel(const float* __restrict__ src, float* __restrict__ dst, size_t n,
+                                                       unsigned long long index_base, unsigned long long* __restrict__ fp) {
+    const size_t n4 = n / 4;
+    unsigned long long acc = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        const float4 v = reinterpret_cast<const float4*>(src)[i];
+        if (COPY) reinterpret_cast<float4*>(dst)[i] = v;
+        if (FP) {
+            const unsigned long long e = index_base + 4 * i;
+            acc += fp_mix(e, v.x) + fp_mix(e + 1, v.y) + fp_mix(e + 2, v.z) + fp_mix(e + 3, v.w);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (size_t i = n4 * 4; i < n; ++i) {
+            const float v = src[i];
+            if (COPY) dst[i] = v;
+            if (FP) acc += fp_mix(index_base + i, v);
+        }
+    if (FP) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        __shared__ unsigned long long s[4];
+        if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) atomicAdd(fp, s[0] + s[1] + s[2] + s[3]);
+    }
+}
+
 unsigned grid_for(size_t n4) {
     size_t g = (n4 + 255) / 256;
     if (g > 256 * 8) g = 256 * 8;
@@ -140,6 +181,21 @@ int madm_ema_update(float* ema, const float* p, size_t n, float alpha, void* str
     MADM_REQUIRE(ema && p && n > 0 && ((uintptr_t)ema % 16) == 0 && ((uintptr_t)p % 16) == 0, "ema_update: bad args");
     ema_kernel<<<grid_for(n / 4), 256, 0, (hipStream_t)stream>>>(ema, p, n, alpha);
     return madm_check_launch("ema_kernel");
+}
+
+int madm_snapshot_f32(const float* src, float* dst, size_t n, unsigned long long index_base, unsigned long long* fingerprint,
+                      void* stream) {
+    MADM_REQUIRE(src && (dst || fingerprint) && n > 0, "snapshot_f32: bad args (null src, no output, or n == 0)");
+    MADM_REQUIRE(((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0 && ((uintptr_t)fingerprint % 8) == 0,
+                 "snapshot_f32: src / dst must be 16-byte aligned (fingerprint: 8)");
+    MADM_REQUIRE(index_base <= (1ull << 32) && (unsigned long long)n <= (1ull << 32) - index_base,
+                 "snapshot_f32: index_base + n exceeds 2^32 (the element index takes the upper 32 bits)");
+    const unsigned grid = grid_for(n / 4);
+    hipStream_t st = (hipStream_t)stream;
+    if (dst && fingerprint) snapshot_kernel<true, true><<<grid, 256, 0, st>>>(src, dst, n, index_base, fingerprint);
+    else if (dst) snapshot_kernel<true, false><<<grid, 256, 0, st>>>(src, dst, n, index_base, nullptr);
+    else snapshot_kernel<false, true><<<grid, 256, 0, st>>>(src, nullptr, n, index_base, fingerprint);
+    return madm_check_launch("snapshot_kernel");
 }
 
 }  // extern "C"

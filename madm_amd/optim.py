@@ -78,6 +78,121 @@ class FlatAdamW:
         torch.autograd.graph.increment_version(self.flat.params)
         return norm
 
+    def _hyper(self, names):
+        return {"betas": [float(b) for b in self.betas], "eps": float(self.eps), "lr": {n: float(self.lr) for n in names},
+                "weight_decay": {n: float(self.weight_decay) for n in names}}
+
+    def state_dict(self, names, tensors=True, m=None, v=None):
+        """As TableAdamW.state_dict (keyed by parameter name; ``names``: one per entry of ``self.flat.params``); the one
+        step count is stored with every parameter, as torch.optim.AdamW does."""
+        names = list(names)
+        state = _moment_state(self, names, self.m if m is None else m, self.v if v is None else v) if tensors \
+            else {n: {} for n in names}
+        for n in names:
+            state[n]["step"] = int(self.step_count)
+        return dict(self._hyper(names), state=state)
+
+    def load_state_dict(self, sd, names):
+        names = list(names)
+        _check_names(names, sd["state"])
+        for k, mine in self._hyper(names).items():
+            _check_hyper(k, mine, dict(sd[k]) if isinstance(mine, dict) else ([float(b) for b in sd[k]] if k == "betas" else float(sd[k])))
+        _load_moments(self, names, sd["state"])
+        steps = {int(sd["state"][n]["step"]) for n in names}
+        if len(steps) != 1:
+            raise ValueError(f"FlatAdamW has one step count for all parameters; the checkpoint holds {sorted(steps)}")
+        self.step_count = steps.pop()
+
+
+_FP_MASK = (1 << 64) - 1
+
+
+def fingerprint_host(values, index_base=0):
+    """The fingerprint of ``madm_snapshot_f32`` (include/madm_hip.h) for a buffer that lives on the HOST: numpy, uint64
+    arithmetic wraps modulo 2^64.  ``values``: a float32 array or CPU tensor; its bit patterns are what counts."""
+    import numpy as np
+    if torch.is_tensor(values):
+        values = values.detach().contiguous().numpy()
+    w = np.ascontiguousarray(values, dtype=np.float32).reshape(-1).view(np.uint32).astype(np.uint64)
+    assert index_base + w.size <= 1 << 32
+    total = 0
+    for lo in range(0, w.size, 1 << 22):        # (bounded temporaries for GB-sized buffers)
+        c = w[lo:lo + (1 << 22)]
+        h = ((np.arange(lo, lo + c.size, dtype=np.uint64) + np.uint64(index_base)) << np.uint64(32)) | c
+        h = h * np.uint64(0x9E3779B97F4A7C15)
+        h ^= h >> np.uint64(32)
+        h = h * np.uint64(0xD6E8FEB86659FD93)
+        h ^= h >> np.uint64(32)
+        total = (total + int(h.sum(dtype=np.uint64))) & _FP_MASK
+    return total
+
+
+def snapshot(src, dst=None, fingerprint=None, index_base=0):
+    """One ``madm_snapshot_f32`` launch on the current stream over the flat fp32 device buffer ``src``: copy into ``dst``
+    (same size; None: no copy) and ADD the fingerprint into ``fingerprint`` (a one-element int64 device tensor holding the
+    uint64's bit pattern, zeroed by the caller; None: no fingerprint)."""
+    _need_cuda(src)
+    assert src.dtype == torch.float32 and src.is_contiguous()
+    if dst is not None:
+        _need_cuda(dst)
+        assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() == src.numel()
+    if fingerprint is not None:
+        _need_cuda(fingerprint)
+        assert fingerprint.dtype == torch.int64 and fingerprint.numel() == 1
+    check(lib.madm_snapshot_f32(src.data_ptr(), None if dst is None else dst.data_ptr(), src.numel(), index_base,
+                                None if fingerprint is None else fingerprint.data_ptr(), _stream()), "madm_snapshot_f32")
+
+
+def fingerprints(buffers):
+    """Fingerprints (python ints below 2^64) of flat fp32 buffers: one launch per device buffer and ONE host sync for all
+    of them, no host copy of the data; buffers on the host go through ``fingerprint_host``."""
+    out = [None] * len(buffers)
+    dev = [i for i, b in enumerate(buffers) if b.is_cuda]
+    if dev:
+        acc = torch.zeros(len(dev), dtype=torch.int64, device=buffers[dev[0]].device)
+        for j, i in enumerate(dev):
+            snapshot(buffers[i], None, acc[j:j + 1])
+        for i, v in zip(dev, acc.tolist()):
+            out[i] = v & _FP_MASK
+    for i, b in enumerate(buffers):
+        if not b.is_cuda:
+            out[i] = fingerprint_host(b)
+    return out
+
+
+def _moment_state(opt, names, m, v):
+    """{name: {"exp_avg", "exp_avg_sq"}}: per-parameter views of the flat moment buffers ``m`` / ``v`` (the optimizer's
+    own, or host copies with the same layout)."""
+    fl = opt.flat
+    assert len(names) == len(fl.params) and len(set(names)) == len(names), "one distinct name per parameter of the table"
+    return {n: {"exp_avg": m[o:o + p.numel()].view(p.shape), "exp_avg_sq": v[o:o + p.numel()].view(p.shape)}
+            for n, p, o in zip(names, fl.params, fl.offsets)}
+
+
+def _check_hyper(what, mine, theirs):
+    if mine != theirs:
+        raise ValueError(f"optimizer state: {what} of the checkpoint ({theirs}) differs from this optimizer's ({mine})")
+
+
+def _check_names(names, state):
+    missing = [n for n in names if n not in state]
+    extra = [n for n in state if n not in set(names)]
+    if missing or extra:
+        raise ValueError(f"optimizer state: parameter names differ (missing {missing[:4]}, unexpected {extra[:4]})")
+
+
+def _load_moments(opt, names, state):
+    """Copies the per-name moments INTO the optimizer's flat buffers (the storage the kernels read is never rebound)."""
+    mine = _moment_state(opt, names, opt.m, opt.v)
+    with torch.no_grad():
+        for n in names:
+            for k in ("exp_avg", "exp_avg_sq"):
+                src = state[n][k]
+                if tuple(src.shape) != tuple(mine[n][k].shape):
+                    raise ValueError(f"optimizer state: {k} of {n} has shape {tuple(src.shape)}, "
+                                     f"expected {tuple(mine[n][k].shape)}")
+                mine[n][k].copy_(src)
+
 
 def ema_update(ema_flat, param_flat, alpha):
     _need_cuda(ema_flat, param_flat)
@@ -215,3 +330,30 @@ class TableAdamW:
                                         scale, _stream()), "madm_adamw_step_table")
         torch.autograd.graph.increment_version(self.flat.params)
         return norm, True
+
+    def state_dict(self, names, tensors=True, m=None, v=None):
+        """torch.optim.AdamW's per-parameter state (``exp_avg``, ``exp_avg_sq``, ``step``) keyed by parameter NAME -- the
+        flat order is an implementation detail (MadmTrainer moves late-finishing tensors to the front) that a checkpoint has
+        to survive -- plus betas / eps / per-tensor lr and weight decay for the consistency check of ``load_state_dict``.
+        ``names``: one name per entry of ``self.flat.params``.  ``tensors=False`` leaves the moments out (the checkpointer
+        adds views of its own snapshot); ``m`` / ``v``: flat buffers with this layout to view instead of the live ones."""
+        names = list(names)
+        state = _moment_state(self, names, self.m if m is None else m, self.v if v is None else v) if tensors \
+            else {n: {} for n in names}
+        for n, t in zip(names, self.steps):
+            state[n]["step"] = int(t)
+        return {"state": state, "betas": [float(b) for b in self.betas], "eps": float(self.eps),
+                "lr": {n: l for n, l in zip(names, self.base_lr)}, "weight_decay": {n: w for n, w in zip(names, self.wd)}}
+
+    def load_state_dict(self, sd, names):
+        """Writes the moments INTO ``self.m`` / ``self.v`` and replaces the step counts; raises ValueError when the names,
+        a shape or a hyper-parameter differ from this optimizer's."""
+        import numpy as np
+        names = list(names)
+        _check_names(names, sd["state"])
+        _check_hyper("betas", [float(b) for b in self.betas], [float(b) for b in sd["betas"]])
+        _check_hyper("eps", float(self.eps), float(sd["eps"]))
+        _check_hyper("lr", {n: l for n, l in zip(names, self.base_lr)}, dict(sd["lr"]))
+        _check_hyper("weight_decay", {n: w for n, w in zip(names, self.wd)}, dict(sd["weight_decay"]))
+        _load_moments(self, names, sd["state"])
+        self.steps = np.asarray([int(sd["state"][n]["step"]) for n in names], dtype=np.int64)

@@ -46,6 +46,7 @@ class MadmTrainer:
 
         table = [t for t in table if late(t[0])] + [t for t in table if not late(t[0])]
         self.opt = optim.TableAdamW(table, betas=betas, eps=eps)
+        self.param_names = [names[id(p)] for p in self.opt.flat.params]     # optimizer state is keyed by these
         self.grad_clip = grad_clip
         self.dist = dist
         self.reducer = GradBucketReducer(self.opt.flat.grad, dist, mode=exchange, wire_dtype=wire_dtype)
@@ -196,6 +197,130 @@ class MadmTrainer:
             self.last_overlap_frac = self.reduced_during_backward / max(1, self.opt.flat.numel)
         out = {k: float(v.detach()) for k, v in loss_dict.items()}       # (the step's host sync)
         return out, norm, stepped
+
+
+    # ---- checkpointing: everything a step reads besides the model's own state_dict (madm_amd/checkpoint.py) ----
+    def _device(self):
+        return self.opt.flat.flat.device
+
+    def _dropout_generators(self):
+        """Explicit generators of the Dropout2d masks (head.py: ``dropout_generator``; None = the device's default one)."""
+        out = {}
+        for key in ("sem_seg_head", "ema_sem_seg_head"):
+            g = getattr(getattr(self.model, key, None), "dropout_generator", None)
+            if g is not None:
+                out[key] = g
+        return out
+
+    def rng_state(self):
+        """Every generator a training step draws from: Python ``random`` (strong-augmentation parameters, the reverse-noise
+        timestep), ``numpy.random`` (ClassMix class choices), torch's CPU generator (colour jitter, MIC mask grid), the
+        device generator of this trainer's GPU (Dropout2d masks, UNet timesteps) and the heads' own dropout generators
+        where one is set.  Plain tensors / numbers / lists only."""
+        import random
+        import numpy as np
+        ver, internal, gauss = random.getstate()
+        kind, keys, pos, has_gauss, cached = np.random.get_state()
+        out = {"python": {"version": int(ver), "state": [int(x) for x in internal], "gauss_next": gauss},
+               "numpy": {"kind": str(kind), "keys": [int(x) for x in keys], "pos": int(pos), "has_gauss": int(has_gauss),
+                         "cached_gaussian": float(cached)},
+               "torch_cpu": torch.get_rng_state().clone()}
+        dev = self._device()
+        if dev.type == "cuda":
+            out["torch_device"] = torch.cuda.get_rng_state(dev).clone()
+        out["dropout_generators"] = {k: g.get_state().clone() for k, g in self._dropout_generators().items()}
+        return out
+
+    def set_rng_state(self, st):
+        import random
+        import numpy as np
+        py, npy = st["python"], st["numpy"]
+        random.setstate((int(py["version"]), tuple(int(x) for x in py["state"]), py["gauss_next"]))
+        np.random.set_state((npy["kind"], np.asarray(npy["keys"], dtype=np.uint32), int(npy["pos"]), int(npy["has_gauss"]),
+                             float(npy["cached_gaussian"])))
+        torch.set_rng_state(st["torch_cpu"].cpu())
+        dev = self._device()
+        if dev.type == "cuda":
+            if "torch_device" not in st:
+                raise ValueError("the checkpoint holds no device generator state (it was written by a CPU trainer)")
+            torch.cuda.set_rng_state(st["torch_device"].cpu(), dev)
+        gens = self._dropout_generators()
+        if set(gens) != set(st.get("dropout_generators", {})):
+            raise ValueError(f"dropout generators differ: checkpoint {sorted(st.get('dropout_generators', {}))}, "
+                             f"this trainer {sorted(gens)}")
+        for k, g in gens.items():
+            g.set_state(st["dropout_generators"][k].cpu())
+
+    def state_dict(self, tensors=True, m=None, v=None):
+        """``iteration``, ``optimizer`` (TableAdamW.state_dict by parameter name), ``grad_scaler`` (torch's GradScaler
+        names), ``model_step`` (``model.train_iter_index``: it drives the EMA alpha and the reverse-noise schedule) and ``rng``.
+        Plain tensors, numbers, strings, lists and dicts only.  ``tensors`` / ``m`` / ``v``: see TableAdamW.state_dict."""
+        return {"iteration": int(self.iter),
+                "optimizer": self.opt.state_dict(self.param_names, tensors=tensors, m=m, v=v),
+                "grad_scaler": {"scale": float(self.scale), "_growth_tracker": int(self._growth_tracker)},
+                "model_step": int(getattr(self.model, "train_iter_index", 0)),
+                "rng": self.rng_state()}
+
+    def load_state_dict(self, sd):
+        """In place: the moments are copied INTO the optimizer's flat buffers, nothing is rebound.  The parameters themselves
+        belong to the model's state_dict (the checkpointer loads them into the same flat storage)."""
+        self.opt.load_state_dict(sd["optimizer"], self.param_names)
+        self.iter = int(sd["iteration"])
+        self.scale = float(sd["grad_scaler"]["scale"])
+        self._growth_tracker = int(sd["grad_scaler"]["_growth_tracker"])
+        if hasattr(self.model, "train_iter_index"):
+            self.model.train_iter_index = int(sd["model_step"])
+        self.set_rng_state(sd["rng"])
+        # parameters may have been loaded through raw views of the flat buffer: move their version counters the way
+        # TableAdamW.step does, so that every packed operand derived from them is rebuilt
+        torch.autograd.graph.increment_version(self.opt.flat.params)
+
+    def flat_buffers(self):
+        """The flat fp32 buffers that hold the bulk of the training state, by name; each maps (tensor, names, offsets,
+        numels): what a checkpointer snapshots with ONE launch each and re-views per name."""
+        fl = self.opt.flat
+        numels = [p.numel() for p in fl.params]
+        out = {"param": (fl.flat, self.param_names, fl.offsets, numels),
+               "exp_avg": (self.opt.m, self.param_names, fl.offsets, numels),
+               "exp_avg_sq": (self.opt.v, self.param_names, fl.offsets, numels)}
+        tf = getattr(self.model, "_ema_teacher_flat", None)
+        if tf is not None:
+            tn = {id(p): n for n, p in self.model.named_parameters()}
+            out["teacher"] = (tf.flat, [tn[id(p)] for p in tf.params], tf.offsets, [p.numel() for p in tf.params])
+        return out
+
+    def flat_layout_signature(self):
+        """{buffer: digest of its (name, offset, numel) rows}: fingerprints depend on position, so they are comparable
+        only between trainers with the same layout."""
+        import hashlib
+        out = {}
+        for k, (t, names, offs, numels) in self.flat_buffers().items():
+            h = hashlib.sha256(f"{t.numel()}".encode())
+            for row in zip(names, offs, numels):
+                h.update(("%s:%d:%d;" % row).encode())
+            out[k] = h.hexdigest()
+        return out
+
+    def state_fingerprints(self):
+        """64-bit fingerprints (madm_snapshot_f32, fingerprint only) of the parameter, exp_avg, exp_avg_sq and teacher buffers:
+        one launch each, one host sync, no host copy of the data."""
+        bufs = self.flat_buffers()
+        return dict(zip(bufs, optim.fingerprints([b[0] for b in bufs.values()])))
+
+    def replicas_in_sync(self):
+        """Whether every data-parallel rank holds the same parameters: all-gathers the parameter fingerprint (8 bytes per
+        rank).  Collective: every rank calls it.  True without a process group."""
+        d = self.dist
+        if d is None or not d.is_initialized() or d.get_world_size() == 1 and not self.reducer.active:
+            return True
+        flat = self.opt.flat.flat
+        fp = optim.fingerprints([flat])[0]
+        fp = fp - (1 << 64) if fp >= (1 << 63) else fp       # (int64 bit pattern)
+        dev = flat.device if d.get_backend() == "nccl" else torch.device("cpu")
+        mine = torch.tensor([fp], dtype=torch.int64, device=dev)
+        got = [torch.zeros_like(mine) for _ in range(d.get_world_size())]
+        d.all_gather(got, mine)
+        return all(int(g.item()) == fp for g in got)
 
 
 class ExtractorTrainer:
