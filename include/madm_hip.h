@@ -609,6 +609,37 @@ int madm_causal_attention_fwd(const madm_attention_args* a, void* stream);
 /* y = x * sigmoid(1.702 x) (CLIP's quick_gelu), evaluated in f32; dtype storage, in place allowed. */
 int madm_quick_gelu(int dtype, const void* x, void* y, size_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * The periodic training picture (modeling/meta_arch/cmdise.py:238-305 vis_results, utils/visualization.py:44-88): the
+ * reference copies every tensor to the host and draws it with PIL / matplotlib; here ONE launch writes the whole RGB8
+ * sheet from a table of tile descriptors.  Every tile kind is an exact integer / f32 recipe (a CPU restatement is bit
+ * exact):
+ *   IMAGE  src f32 [B][3][H][W]: v = clip(x * p0 + p1, 0, 1) (product and sum rounded separately), byte =
+ *          (int)floorf(fmaf(255, v, 0.5f)), NaN -> 0
+ *   LABEL  src i64 [B][H][W]: RGB = palette768[3 * (l & 255) ..] (255 -> the zero padding: black, as colorize_mask)
+ *   LOGITS src f32 [B][C][h][w]: where (h, w) != (H, W) the value at an output pixel is the align_corners=False
+ *          bilinear sample (madm_resize_bilinear's arithmetic: four weights, one sum), evaluated per pixel and class in
+ *          the kernel -- no [B][C][H][W] tensor exists; then the FIRST maximal class, coloured through the palette
+ *          (softmax does not move an argmax: cmdise.py:254-268)
+ *   HEAT   src f32 [B][H][W]: t = (int)(255 * clip(v, 0, 1)), u = t / 255, r = clip(1.5 - |4u - 3|), g = clip(1.5 -
+ *          |4u - 2|), b = clip(1.5 - |4u - 1|), each to a byte as for images (NaN -> t = 0)
+ * ------------------------------------------------------------------------------- */
+typedef enum { MADM_VIS_IMAGE = 0, MADM_VIS_LABEL = 1, MADM_VIS_LOGITS = 2, MADM_VIS_HEAT = 3 } madm_vis_kind;
+#define MADM_VIS_MAX_TILES 16
+typedef struct {
+    int kind;          /* madm_vis_kind */
+    const void* src;   /* device pointer, layout by kind */
+    int C;             /* IMAGE: 3; LOGITS: number of classes; LABEL / HEAT: 1 */
+    int h, w;          /* spatial size of src: (H, W) except for LOGITS */
+    float p0, p1;      /* IMAGE: scale, shift */
+} madm_vis_tile;
+/* canvas u8 [rows*H][cols*W][3], cols = min(cols_max, n), rows = B * ceil(n / cols_max); tile i of image j at column
+ * i % cols_max, row j * ceil(n / cols_max) + i / cols_max (cmdise.py:250,261).  EVERY byte of the canvas is written: the
+ * blank cells of a ragged last row come out 255.  ``tiles`` is a HOST array of n <= MADM_VIS_MAX_TILES descriptors (it
+ * travels as kernel arguments: no copy, no synchronisation). */
+int madm_vis_compose(const madm_vis_tile* tiles, int n, int B, int H, int W, int cols_max,
+                     const unsigned char* palette768, unsigned char* canvas, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,14 @@ class AttentionBwdArgs(ctypes.Structure):
     ]
 
 
+VIS_IMAGE, VIS_LABEL, VIS_LOGITS, VIS_HEAT = 0, 1, 2, 3
+VIS_MAX_TILES = 16
+
+
+class VisTile(ctypes.Structure):
+    _fields_ = [("kind", c_int), ("src", c_void_p), ("C", c_int), ("h", c_int), ("w", c_int), ("p0", c_float), ("p1", c_float)]
+
+
 # every symbol include/madm_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("madm_abi_version", c_int, []),
@@ -213,6 +221,7 @@ SYMBOLS = [
     ("madm_token_embedding", c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     ("madm_causal_attention_fwd", c_int, [ctypes.POINTER(AttentionArgs), c_void_p]),
     ("madm_quick_gelu", c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("madm_vis_compose", c_int, [ctypes.POINTER(VisTile), c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 ]
 
 

@@ -23,12 +23,18 @@ mask and its own pseudo labels in the masked CE -- the same values at B = 1 (DES
 
 Options of the reference that no shipped config enables (mask_diff, noise_reg, denoise_supervise, fd, fd_attention,
 merge_with_pl_data, remove_amp / remove_texture, sem_seg_head_sec_modal=True, prompt masking) raise NotImplementedError.
-``reg_uncertain`` only feeds the reference's visualisation (:323-328 -> vis_data :556-560); it is accepted and changes nothing
-but the teacher call's ``return_unet_final_output`` (which the VAE-decoder branch computes anyway).  The periodic matplotlib
-dump (``vis_results``) is out of scope.
+``reg_uncertain`` only feeds the reference's visualisation (:327-333 -> vis_data :596-601); it changes nothing in a step
+but the teacher call's ``return_unet_final_output`` (which the VAE-decoder branch computes anyway).
+
+The periodic picture (``vis_period`` / ``output_dir``, :552-653 + cmdise.py:238-305): every ``vis_period`` iterations
+``<output_dir>/vis_results/{iter:06d}_rank{local_rank}.png`` with the reference's tiles in its order, composed by one HIP
+launch on the training stream and written in line or, with ``vis_async=True``, by a writer thread (vis.py; DESIGN.md, the periodic training picture).  The
+reference's extra picture-only teacher pass (:603-644) runs too, with its generator draws and BatchNorm side effects.  Off
+(``None`` / 0, the default) nothing is allocated, no generator is touched, no thread exists.
 """
 import os
 import random
+import time
 from copy import deepcopy
 
 import numpy as np
@@ -51,7 +57,8 @@ class MTMADISE(MadmInference):
                  sem_seg_head_sec_modal=False, ema_alpha=0.999, pseudo_threshold=0.968, blur=True, color_jitter_strength=0.2,
                  color_jitter_probability=0.2, enable_mixup=True, pl_crop=False, color_aug_flag=True, ema_w_unet=False,
                  pixel_mean=(0.0, 0.0, 0.0), pixel_std=(255.0, 255.0, 255.0), size_divisibility=64, color_aug=None,
-                 mic=False, mask_ratio=None, mic_reg=False, MIC_reg_wo_pl_val=False, **unsupported):
+                 mic=False, mask_ratio=None, mic_reg=False, MIC_reg_wo_pl_val=False, vis_period=None, output_dir=None,
+                 vis_max_cols=5, vis_denorm=(0.5, 0.5), vis_async=False, **unsupported):
         for k, v in unsupported.items():
             if k in ("mask_diff", "noise_reg", "denoise_supervise", "fd", "fd_attention",
                      "merge_with_pl_data", "remove_amp", "remove_texture", "prompt_confidence",
@@ -91,6 +98,29 @@ class MTMADISE(MadmInference):
         self.mask_block_size = 32
         self.deferred_mask_flags = None     # a list: the trainer collects the range flags of mask_image and raises at its end
         self.train_palette = L.pad_palette(train_palette)                       # mtmadise.py:97-99
+        # the periodic picture (cmdise.py:212-215,231; mtmadise.py:552): None / 0 = off
+        self.vis_period = int(vis_period) if vis_period else None
+        if self.vis_period is not None and self.vis_period < 0:
+            raise ValueError(f"vis_period must be a positive number of iterations (None / 0: off), got {vis_period!r}")
+        if self.vis_period and not output_dir:
+            raise ValueError("vis_period needs output_dir: the pictures go to <output_dir>/vis_results")
+        self.output_dir, self.vis_max_cols = output_dir, int(vis_max_cols)
+        if self.vis_max_cols < 1 or len(tuple(vis_denorm)) != 2:
+            raise ValueError("vis_max_cols must be >= 1 and vis_denorm a (scale, shift) pair")
+        self.vis_denorm = (float(vis_denorm[0]), float(vis_denorm[1]))
+        self.vis_writer = self.last_vis = None
+        # vis_async: the writer thread is off by default until tools/bench_vis.py has shown its training-thread cost below the
+        # in-line host approach's on an MI355X (the periodic training picture: not measured yet)
+        self._vis_classes = len(list(train_palette)) // 3      # reg_target_tensor is built from the UNPADDED palette (:92-94)
+        self._vis_reg_target = None
+        if self.vis_period:
+            from . import vis, dist as _dist
+            n_tiles = 8 + (2 if (mic or mic_reg) else 0) + sum(c in self.vae_decoder_loss for c in 'st') + \
+                (3 if reg_uncertain else 0) + ((2 if 's' in self.vae_decoder_loss else 1) if rev_noise_sup else 0)
+            if n_tiles > vis.MAX_TILES:
+                raise ValueError(f"this configuration's picture has {n_tiles} tiles, a sheet holds {vis.MAX_TILES}: "
+                                 "switch vis_period off or drop an option that only adds tiles")
+            self.vis_writer = vis.VisWriter(output_dir, rank=_dist.env_world()[1], async_write=vis_async)
         if reg_target_palette is None:
             self.reg_target_palette = list(self.train_palette)
         else:
@@ -265,8 +295,9 @@ class MTMADISE(MadmInference):
                 if self.rev_noise_gradually:
                     t_ = int(t_ * (1 - self.train_iter_index / self.rev_noise_end_iter))
                 kw['timestep'] = (t_, t_ + 1)
+            pl_out = None
             if self.reg_uncertain:
-                low_res_feats, _ = self.backbone(target, return_unet_final_output=True, **kw)
+                low_res_feats, pl_out = self.backbone(target, return_unet_final_output=True, **kw)
             else:
                 low_res_feats = self.backbone(target, **kw)
             head_t = self.ema_sem_seg_head
@@ -381,8 +412,113 @@ class MTMADISE(MadmInference):
             self.last_step.update(masked_img=masked_img, mask_grid=mask_u)
             if self.mic:
                 self.last_step['masked_logits'] = masked_logits
+        if self.vis_period and self.train_iter_index % self.vis_period == 0:
+            if overlap and pl_out is not None:
+                pl_out['after_vae.decoder'].record_stream(main_stream)
+            self._vis_dump(source=source, target=target, gt=gt, source_out=source_out, target_out=target_out,
+                           masked_out=masked_out if self.mic_reg else None, pl_out=pl_out, pseudo_prob=pseudo_prob,
+                           pl_timestep=kw.get('timestep'))
         outs = _TrainStepFn.apply(state, len(names), *[losses[n] for n in names], *params)
         return dict(zip(names, outs))
+
+    # ------------------------------------------------------------------ the periodic picture (mtmadise.py:552-653)
+    def _vis_logits(self, tok):
+        """Head output tokens -> f32 [B, K, h, w] (the sheet's kernel resizes and takes the argmax)."""
+        K = self.sem_seg_head.num_classes
+        return ops.nhwc_to_nchw(tok.t, tok.B, K, tok.H, tok.W)
+
+    def vis_tiles(self, *, source, target, gt, source_out, target_out, masked_out, pl_out, pseudo_prob, pl_timestep):
+        """The reference's ``vis_data`` (:559-601) in its order, from what the step already holds (``last_step`` + the
+        decoder outputs).  Decoder images stay in [-1, 1] and carry their own (0.5, 0.5) denorm: the reference's
+        ``(x + 1) / 2``.  The pseudo-label tile is drawn from ``pseudo_label`` itself -- the argmax of the up-sampled teacher
+        logits that the step trained on, the same picture as the reference's logits tile."""
+        ls = self.last_step
+        pl_info = 'target_sec_modal_pl'
+        if pl_timestep is not None and self.train_iter_index <= self.rev_noise_end_iter:      # :556-557, after the += 1
+            pl_info += '_{}_t'.format(pl_timestep[0])
+        half = (0.5, 0.5)
+        tiles = [
+            dict(data_type='image', info='source_rgb', data=source),
+            dict(data_type='logits', info='source_pred', data=self._vis_logits(ls['source_logits'])),
+            dict(data_type='label', info='source_label', data=gt),
+            dict(data_type='image', info='target_sec_modal', data=target),
+            dict(data_type='label', info=pl_info, data=ls['pseudo_label']),
+            dict(data_type='image', info='mixup_modal', data=ls['mixed_img']),
+            dict(data_type='logits', info='mixup_pred', data=self._vis_logits(ls['target_logits'])),
+            dict(data_type='label', info='mixup_label', data=ls['mixed_lbl']),
+        ]
+        if self.mic or self.mic_reg:                                  # :571-576
+            tiles.append(dict(data_type='image', info='masked_image', data=ls['masked_img']))
+            if self.mic:
+                tiles.append(dict(data_type='logits', info='masked_image_pred', data=self._vis_logits(ls['masked_logits'])))
+            else:
+                tiles.append(dict(data_type='image', info='masked_vae_decoder_out', data=masked_out['after_vae.decoder'],
+                                  denorm=half))
+        if 's' in self.vae_decoder_loss:
+            tiles.append(dict(data_type='image', info='source_vae_decoder_out', data=source_out['after_vae.decoder'],
+                              denorm=half))
+        if 't' in self.vae_decoder_loss:
+            tiles.append(dict(data_type='image', info='target_vae_decoder_out', data=target_out['after_vae.decoder'],
+                              denorm=half))
+        if self.reg_uncertain:                                        # :329-333, 596-601
+            if self._vis_reg_target is None:
+                pal = torch.tensor(self.train_palette[:3 * self._vis_classes], dtype=torch.float32, device=source.device)
+                self._vis_reg_target = (pal / 255.0).reshape(self._vis_classes, 3).t().reshape(1, 3, -1, 1, 1).contiguous()
+            after01 = (pl_out['after_vae.decoder'] + 1) / 2
+            prob_reg = 1 / (torch.norm(after01[:, :, None] - self._vis_reg_target, dim=1) + 1e-3)
+            pseudo_prob_reg = torch.softmax(prob_reg, dim=1).max(dim=1)[0]
+            tiles += [dict(data_type='logits', info='pl_reg', data=prob_reg),
+                      dict(data_type='heatmap', info='pl_prob_reg', data=pseudo_prob_reg),
+                      # the share of confident pixels stays a device scalar: the writer thread formats the title
+                      dict(data_type='heatmap', info='pl_prob_{:.3f}', data=pseudo_prob,
+                           info_value=ls['pseudo_weight'].reshape(-1)[-1:].clone())]
+        return tiles
+
+    def _vis_extra_pass(self, target):
+        """The reference's picture-only pass (:603-644): the STUDENT backbone under the target adapter and the EMA head on
+        the target image -- without noise up to ``rev_noise_end_iter``, afterwards at a ``random.randint`` timestep of
+        ``denoise_timestep_range``.  Its generator draws (noise, dropout, that randint) and the BatchNorm statistics it moves
+        are the reference's."""
+        if not self.rev_noise_sup:
+            return []
+        kw, tag = dict(input_modal='others'), 'no_noise_t'
+        if self.train_iter_index > self.rev_noise_end_iter:
+            t_ = random.randint(self.denoise_timestep_range[0], self.denoise_timestep_range[1])
+            kw['timestep'] = (t_, t_ + 1)
+            tag = 'noise_{}_t'.format(t_)
+        tiles = []
+        self.set_lora_adapter(state=self.target_modality)
+        if 's' in self.vae_decoder_loss:
+            feats, out = self.backbone(target, return_unet_final_output=True, **kw)
+            tiles.append(dict(data_type='image', info=tag + '_reg', data=out['after_vae.decoder'], denorm=(0.5, 0.5)))
+        else:
+            feats = self.backbone(target, **kw)
+        head_t = self.ema_sem_seg_head
+        logits = head_t.forward_tokens([feats['output_features'].tok[k] for k in head_t.in_keys])
+        tiles.append(dict(data_type='logits', info=tag + '_pred', data=self._vis_logits(logits)))
+        return tiles
+
+    def _vis_dump(self, **held):
+        from . import vis
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            ev[0].record()
+            extra = self._vis_extra_pass(held['target'])
+            ev[1].record()
+            t1 = time.perf_counter()
+            tiles = self.vis_tiles(**held) + extra
+            canvas = self.vis_writer.submit(self.train_iter_index, tiles, cols_max=self.vis_max_cols,
+                                            palette=self.train_palette, denorm=self.vis_denorm)
+            ev[2].record()
+        B = held['source'].shape[0]
+        H, W = held['source'].shape[-2:]
+        # kept until the next dump.  For tools: ``events`` = (start, picture-only pass done, sheet composed) on the training
+        # stream, ``host_ms`` = what the call cost the training thread (picture-only pass, tile list + submit)
+        self.last_vis = dict(iteration=self.train_iter_index, infos=[t['info'] for t in tiles], canvas=canvas,
+                             meta=vis.VisWriter.describe(tiles, B, H, W, self.vis_max_cols),
+                             path=self.vis_writer.path(self.train_iter_index), events=ev,
+                             host_ms=((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3))
 
     def unused_lora_parameters(self, used_modal):
         """The tensors ``add_zero_gead_on_unused_lora`` sums (mtmadise.py:149-157): every UNet parameter whose name holds

@@ -1022,6 +1022,28 @@ def argmax_nchw(x):
     return out
 
 
+def vis_compose(tiles, B, H, W, cols_max, palette, canvas):
+    """One launch: the RGB8 sheet ``canvas`` u8 [rows*H, cols*W, 3] from ``tiles`` = [(kind, tensor, p0, p1), ...] (at most
+    16; kinds _lib.VIS_*; tensor layouts in include/madm_hip.h); ``palette`` u8 [768] on the device.  Every byte of the
+    canvas is written."""
+    n = len(tiles)
+    per_img = -(-n // cols_max) if cols_max > 0 and n else 0
+    _need_cuda(palette, canvas, *[t[1] for t in tiles])
+    assert canvas.dtype == torch.uint8 and canvas.is_contiguous() and palette.dtype == torch.uint8 and palette.numel() == 768
+    assert canvas.numel() == B * per_img * H * min(cols_max, n) * W * 3, "canvas size does not match the layout"
+    want = {_lib.VIS_IMAGE: torch.float32, _lib.VIS_LABEL: torch.int64, _lib.VIS_LOGITS: torch.float32,
+            _lib.VIS_HEAT: torch.float32}
+    table = (_lib.VisTile * max(n, 1))()
+    for d, (kind, t, p0, p1) in zip(table, tiles):
+        assert t.dtype == want[kind] and t.is_contiguous() and t.shape[0] == B and t.dim() == (3 if kind in (
+            _lib.VIS_LABEL, _lib.VIS_HEAT) else 4), f"vis tile kind {kind}: {t.dtype} {tuple(t.shape)}"
+        d.kind, d.src, d.C = kind, t.data_ptr(), (t.shape[1] if t.dim() == 4 else 1)
+        d.h, d.w, d.p0, d.p1 = t.shape[-2], t.shape[-1], p0, p1
+    check(lib.madm_vis_compose(table, n, B, H, W, cols_max, palette.data_ptr(), canvas.data_ptr(), _stream()),
+          "madm_vis_compose")
+    return canvas
+
+
 def scale_pad_nchw(x, scale, OH, OW, y1=0, x1=0, out=None):
     """x[:, :, y1:y1+OH, x1:x1+OW] * scale with zeros outside x (f32 NCHW): padding, cropping, window extraction."""
     _need_cuda(x, out)
