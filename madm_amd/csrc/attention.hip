@@ -58,14 +58,13 @@ struct AttnCfg {
 typedef unsigned int u32x4a __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2a __attribute__((ext_vector_type(2)));
 #if defined(__HIP_DEVICE_COMPILE__)
-template <int N> __device__ __forceinline__ void attn_wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
 // waits until at most ``young`` LDS reads issued after the awaited one are outstanding (young is a constant after unrolling)
 __device__ __forceinline__ void attn_wait_young(int young) {
-    if (young >= 4) attn_wait_lgkm<4>();
-    else if (young == 3) attn_wait_lgkm<3>();
-    else if (young == 2) attn_wait_lgkm<2>();
-    else if (young == 1) attn_wait_lgkm<1>();
-    else attn_wait_lgkm<0>();
+    if (young >= 4) wait_lgkmcnt<4>();
+    else if (young == 3) wait_lgkmcnt<3>();
+    else if (young == 2) wait_lgkmcnt<2>();
+    else if (young == 1) wait_lgkmcnt<1>();
+    else wait_lgkmcnt<0>();
 }
 #endif
 
@@ -252,7 +251,7 @@ __global__ __launch_bounds__(NW * 64, NQ > 1 ? 2 : 1) void attn_kernel(const Att
             constexpr int NIT = NKB * NS, KD = 4;
             const unsigned kbase = (unsigned)(size_t)Ks + (unsigned)(fi * C::QK_ROWB + fg * 16);
             u32x4a kf[KD + 1];
-            attn_wait_lgkm<0>();          // nothing of the compiler's is left on the counter the waits below count on
+            wait_lgkmcnt<0>();          // nothing of the compiler's is left on the counter the waits below count on
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < KD && i < NIT; ++i)

@@ -221,6 +221,12 @@ __device__ __forceinline__ void kernarg_touch() {
 #endif
 }
 
+// counted waits of the hand-scheduled kernels (LDS-DMA rings, inline-asm LDS reads); gfx asm: device pass only
+#if defined(__HIP_DEVICE_COMPILE__)
+template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+template <int N> __device__ __forceinline__ void wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
+#endif
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: set it once per device (bit per
 // device id in ``done``, atomic: host threads may launch concurrently).  ``done`` is a function-local static of the caller,
 // i.e. one per kernel instantiation.

@@ -36,17 +36,8 @@ __global__ __launch_bounds__(256, (NWS == 2 || BN == 64) ? 2 : 1) void conv3x3_h
     const int frow = lane & 15, fg = lane >> 4;
     const int z = blockIdx.z;
 
-    int bid = blockIdx.x;   // XCD-aware order (see igemm.hip)
-    {
-        const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = bid & 7, i = bid >> 3;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
-    const int tm = magic_div(bid, pd.m_tilesN), tn = bid - tm * p.tilesN;
-    const int n0 = tn * BN;
-    const int b = magic_div(tm, pd.m_ppi);
-    const int pr = tm - b * pd.patchesPerImg;
-    const int pry = magic_div(pr, pd.m_px);
-    const int py0 = pry * TH, px0 = (pr - pry * pd.patchesX) * TW;
+    const int bid = xcd_block_order();
+    HALO_PATCH_POS(BN, TH, TW, p, pd, bid);
 
     // ---- per-thread staging state ----
     int pixoff[HI], hpos[HI];
@@ -66,14 +57,11 @@ __global__ __launch_bounds__(256, (NWS == 2 || BN == 64) ? 2 : 1) void conv3x3_h
         const int n = n0 + lrow + 32 * i;
         wvoff[i] = (n < p.N) ? (unsigned)(((size_t)n * p.ldw + cpos * EPC) * sizeof(T)) : OOB;
     }
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in1, 0, p.bytes1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in2 ? p.in2 : p.in1), 0,
-                                                                         p.in2 ? p.bytes2 : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.bytesw, 0x00020000);
+    IGEMM_OPERAND_DESCRIPTORS(p);
 
     const int nchunks = p.Ctot / BKE;
-    const int ck0 = (nchunks * z) / p.splitk;
-    const int ck1 = (nchunks * (z + 1)) / p.splitk;
+    const KSlice slice = splitk_slice(nchunks, z, p.splitk);
+    const int ck0 = slice.k0, ck1 = slice.k1;
     const int S = (ck1 - ck0) * 9;
 
     static_assert(NWS >= 2 && NWS % 2 == 0, "the weight ring must have an even number of stages");
@@ -85,40 +73,13 @@ __global__ __launch_bounds__(256, (NWS == 2 || BN == 64) ? 2 : 1) void conv3x3_h
 #pragma unroll
     for (int j = 0; j < EPC; ++j) { sc[j] = 1.f; sh[j] = 0.f; }
 
-#define C3_LOAD_HALO(ck)                                                                            \
-    {                                                                                               \
-        const int c0_ = (ck) * BKE;                                                                 \
-        const bool first_ = c0_ < p.C1;                                                             \
-        const __amdgpu_buffer_rsrc_t rs_ = first_ ? rs1 : rs2;                                      \
-        const int ld_ = first_ ? p.ld1 : p.ld2;                                                     \
-        const int cofs_ = (first_ ? c0_ : c0_ - p.C1) + cpos * EPC;                                 \
-        _Pragma("unroll") for (int i = 0; i < HI; ++i) {                                            \
-            const unsigned off_ = (unsigned)(pixoff[i] * ld_ + cofs_) * (unsigned)sizeof(T);        \
-            hr[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_, pixoff[i] >= 0 ? off_ : OOB, 0, 0);  \
-        }                                                                                           \
-        if (FUSE) {                                                                                 \
-            const float* gs_ = p.gn_gamma + c0_ + cpos * EPC;   /* raw gamma / beta; C3_STORE_HALO */     \
-            const float* gh_ = p.gn_beta + c0_ + cpos * EPC;    /* turns them into scale / shift   */     \
-            _Pragma("unroll") for (int j = 0; j < EPC; j += 4) {                                    \
-                const float4 a_ = *reinterpret_cast<const float4*>(gs_ + j);                        \
-                const float4 b_ = *reinterpret_cast<const float4*>(gh_ + j);                        \
-                sc[j] = a_.x; sc[j + 1] = a_.y; sc[j + 2] = a_.z; sc[j + 3] = a_.w;                 \
-                sh[j] = b_.x; sh[j + 1] = b_.y; sh[j + 2] = b_.z; sh[j + 3] = b_.w;                 \
-            }                                                                                       \
-        }                                                                                           \
-    }
-
 #define C3_STORE_HALO(buf, ck_)                                                                     \
     {                                                                                               \
         u32x4* dst_ = halo + (buf) * HALO_U4;                                                       \
         if (FUSE) {                                                                                 \
             const unsigned cb_ = (unsigned)((ck_) * BKE + cpos * EPC);                              \
-            _Pragma("unroll") for (int j = 0; j < EPC; ++j) {                                       \
-                const float2 st_ = gstat[__umulhi(cb_ + j, p.gn_magic)];                            \
-                const float s_ = st_.y * sc[j];                                                     \
-                sh[j] = sh[j] - st_.x * s_;                                                         \
-                sc[j] = s_;                                                                         \
-            }                                                                                       \
+            _Pragma("unroll") for (int j = 0; j < EPC; ++j)                                         \
+                gn_fold_affine(gstat[__umulhi(cb_ + j, p.gn_magic)], sc[j], sh[j]);                 \
         }                                                                                           \
         _Pragma("unroll") for (int i = 0; i < HI; ++i) {                                            \
             if (hpos[i] >= 0) {                                                                     \
@@ -155,7 +116,7 @@ __global__ __launch_bounds__(256, (NWS == 2 || BN == 64) ? 2 : 1) void conv3x3_h
         for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     if (S > 0) {
-        C3_LOAD_HALO(ck0);
+        HALO_LOAD_CHUNK(ck0);
         C3_LOAD_W(rw[0]);
         if constexpr (NWS == 2) {
             if (S > 1) C3_LOAD_W(rw[1]);
@@ -196,7 +157,7 @@ __global__ __launch_bounds__(256, (NWS == 2 || BN == 64) ? 2 : 1) void conv3x3_h
         const bool next_chunk_ = (ck + 1 < ck1);                                                    \
         C3_STAMP(s_, 0);                                                                            \
         if ((s_) + NWS < S) C3_LOAD_W(RL_);                                                           \
-        if (tap == 0 && next_chunk_) C3_LOAD_HALO(ck + 1);                                          \
+        if (tap == 0 && next_chunk_) HALO_LOAD_CHUNK(ck + 1);                                         \
         C3_PIN();                                                                                   \
         C3_PRIO(1);                                                                                 \
         {                                                                                           \
@@ -246,29 +207,15 @@ __global__ __launch_bounds__(256, (NWS == 2 || BN == 64) ? 2 : 1) void conv3x3_h
 #undef C3_STEP
 #undef C3_LOAD_W
 #undef C3_STORE_W
-#undef C3_LOAD_HALO
 #undef C3_STORE_HALO
 
     halo_tile_epilogue<T, BN>(p, acc, b, py0, px0, n0, z, reinterpret_cast<float*>(smem_raw));
 }
 
 template <typename T, int BN, bool FUSE, int NWS>
-int launch_one(const IgemmP& p0, hipStream_t s) {
-    IgemmP p = p0;
+int launch_one(const IgemmP& p, hipStream_t s) {
     constexpr size_t lds = (size_t)(2 * HPIX * 8 + 2 * BN * 8) * 16 + 32 * sizeof(float2);
-    auto kern = conv3x3_halo_kernel<T, BN, FUSE, NWS>;
-    static std::atomic<uint64_t> attr_done{0};
-    if (int e = madm_raise_dynamic_lds(reinterpret_cast<const void*>(kern), (size_t)(lds), attr_done, "conv3x3")) return e;
-    const int patchesX = (p.OW + TW - 1) / TW, patchesY = (p.OH + TH - 1) / TH;
-    p.tilesN = (p.N + BN - 1) / BN;
-    dim3 grid((unsigned)(p.B * patchesX * patchesY * p.tilesN), 1, (unsigned)p.splitk);
-    PatchDecode pd;
-    if (!patch_decode_fill(pd, patchesX, patchesY, p.tilesN, (long long)grid.x)) {
-        madm_set_error("conv3x3: grid of %u blocks too large for the reciprocal patch decode", grid.x);
-        return MADM_ERR_INVALID_ARG;
-    }
-    kern<<<grid, 256, lds, s>>>(p, pd);
-    return madm_check_launch("conv3x3_halo_kernel");
+    return launch_halo_patches<conv3x3_halo_kernel<T, BN, FUSE, NWS>, BN, TH, TW>(p, lds, s, "conv3x3", "conv3x3_halo_kernel");
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
-// Shared by conv3x3.hip (register-staged weights) and conv3x3_dma.hip (LDS-DMA weights): patch geometry, the fused
-// GroupNorm transform of one staged chunk and the patch epilogue.
+// Shared by the halo-tile 3x3 convs -- conv3x3.hip (8 x 16 patches, register-staged weights), conv3x3_dma.hip (LDS-DMA weights)
+// and conv3x3_h16.hip (16 x 16 patches): the block -> patch decode and the one launcher of all three; for the two 8 x 16 kernels
+// also the patch geometry, the load of one halo chunk, its fused GroupNorm transform and the patch epilogue.
 #pragma once
 #include "igemm_common.hpp"
 
@@ -21,6 +22,34 @@ __host__ inline bool patch_decode_fill(PatchDecode& pd, int patchesX, int patche
            (unsigned long long)pd.patchesPerImg * (unsigned)patchesX < lim;
 }
 __device__ __forceinline__ int magic_div(int x, unsigned m) { return m ? (int)__umulhi((unsigned)x, m) : x; }
+// Declares n0, b, py0, px0 of block `bid` (after xcd_block_order) of a grid of BN-channel tiles x PH x PW-pixel patches: first
+// channel, image, patch origin (macro text: as an inline function it changed the 16 x 16 kernel's prologue)
+#define HALO_PATCH_POS(BN, PH, PW, p, pd, bid)                                                  \
+    const int tm = magic_div((bid), (pd).m_tilesN), tn = (bid) - tm * (p).tilesN;               \
+    const int n0 = tn * (BN);                                                                   \
+    const int b = magic_div(tm, (pd).m_ppi);                                                    \
+    const int pr = tm - b * (pd).patchesPerImg;                                                 \
+    const int pry = magic_div(pr, (pd).m_px);                                                   \
+    const int py0 = pry * (PH), px0 = (pr - pry * (pd).patchesX) * (PW)
+
+// The launch of a halo kernel: KERN = the instantiation (the once-per-device raise of its dynamic LDS is therefore per
+// instantiation), on PH x PW-pixel patches and BN-channel tiles; `what` names the kernel family in error texts.
+template <auto KERN, int BN, int PH, int PW>
+int launch_halo_patches(const IgemmP& p0, size_t lds, hipStream_t s, const char* what, const char* kernel_name) {
+    IgemmP p = p0;
+    static std::atomic<uint64_t> attr_done{0};
+    if (int e = madm_raise_dynamic_lds(reinterpret_cast<const void*>(KERN), lds, attr_done, what)) return e;
+    const int patchesX = (p.OW + PW - 1) / PW, patchesY = (p.OH + PH - 1) / PH;
+    p.tilesN = (p.N + BN - 1) / BN;
+    dim3 grid((unsigned)(p.B * patchesX * patchesY * p.tilesN), 1, (unsigned)p.splitk);
+    PatchDecode pd;
+    if (!patch_decode_fill(pd, patchesX, patchesY, p.tilesN, (long long)grid.x)) {
+        madm_set_error("%s: grid of %u blocks too large for the reciprocal patch decode", what, grid.x);
+        return MADM_ERR_INVALID_ARG;
+    }
+    KERN<<<grid, 256, lds, s>>>(p, pd);
+    return madm_check_launch(kernel_name);
+}
 
 namespace {
 
@@ -38,6 +67,39 @@ __device__ __forceinline__ u32x4 gn_act_chunk(u32x4 raw, const float* sc, const 
     act_inplace<EPC>(f, act);
     return __builtin_bit_cast(u32x4, f32_to_chunk<T>(f));
 }
+
+// {mean, rstd} of a channel's group folded into its staged gamma / beta: y = x * sc + sh with sc = rstd gamma, sh = beta - mean sc
+__device__ __forceinline__ void gn_fold_affine(float2 st, float& sc, float& sh) {
+    const float s = st.y * sc;
+    sh = sh - st.x * s;
+    sc = s;
+}
+
+// Requests halo chunk `ck` (HI 16-byte pieces per thread into hr[], zeros outside the map) and, FUSE, the raw gamma / beta of
+// its channels into sc[] / sh[].  A macro over the kernel's locals, not a function: with the arrays passed by reference the
+// compiler's alias analysis -- and with it the counted waits of conv3x3_dma.hip -- changed.
+#define HALO_LOAD_CHUNK(ck)                                                                         \
+    {                                                                                               \
+        const int c0_ = (ck) * BKE;                                                                 \
+        const bool first_ = c0_ < p.C1;                                                             \
+        const __amdgpu_buffer_rsrc_t rs_ = first_ ? rs1 : rs2;                                      \
+        const int ld_ = first_ ? p.ld1 : p.ld2;                                                     \
+        const int cofs_ = (first_ ? c0_ : c0_ - p.C1) + cpos * EPC;                                 \
+        _Pragma("unroll") for (int i = 0; i < HI; ++i) {                                            \
+            const unsigned off_ = (unsigned)(pixoff[i] * ld_ + cofs_) * (unsigned)sizeof(T);        \
+            hr[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_, pixoff[i] >= 0 ? off_ : OOB, 0, 0);  \
+        }                                                                                           \
+        if (FUSE) {                                                                                 \
+            const float* gs_ = p.gn_gamma + c0_ + cpos * EPC;   /* raw gamma / beta; the kernel's */ \
+            const float* gh_ = p.gn_beta + c0_ + cpos * EPC;    /* STORE_HALO folds {mean, rstd} in */ \
+            _Pragma("unroll") for (int j = 0; j < EPC; j += 4) {                                    \
+                const float4 a_ = *reinterpret_cast<const float4*>(gs_ + j);                        \
+                const float4 b_ = *reinterpret_cast<const float4*>(gh_ + j);                        \
+                sc[j] = a_.x; sc[j + 1] = a_.y; sc[j + 2] = a_.z; sc[j + 3] = a_.w;                 \
+                sh[j] = b_.x; sh[j + 1] = b_.y; sh[j + 2] = b_.z; sh[j + 3] = b_.w;                 \
+            }                                                                                       \
+        }                                                                                           \
+    }
 
 // ---- patch epilogue shared by the register-staged and the LDS-DMA halo kernels ----
 // lane: pixel = patch row wm*4+i, column frow; channels n .. n+3.  ``red`` = >= 4 * BN floats of LDS nobody reads any more.

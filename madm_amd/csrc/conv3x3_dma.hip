@@ -12,11 +12,6 @@
 
 namespace {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-template <int N> __device__ __forceinline__ void c3_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void c3_wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-#endif
-
 #ifdef C3D_STAMPS   // tools/exp/stamps_c3d.py: block timeline (block 5 / thread 0) + per-tap stamps of the first chunks
 __device__ unsigned long long g_c3d_stamps[256];
 #define C3D_STAMP(k_) if (blockIdx.x == 5 && blockIdx.z == 0 && threadIdx.x == 0 && (k_) < 256) g_c3d_stamps[(k_)] = __builtin_readcyclecounter();
@@ -51,17 +46,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
     const int frow = lane & 15, fg = lane >> 4;
     const int z = blockIdx.z;
 
-    int bid = blockIdx.x;   // XCD-aware order (see igemm.hip)
-    {
-        const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = bid & 7, i = bid >> 3;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
-    const int tm = magic_div(bid, pd.m_tilesN), tn = bid - tm * p.tilesN;
-    const int n0 = tn * BN;
-    const int b = magic_div(tm, pd.m_ppi);
-    const int pr = tm - b * pd.patchesPerImg;
-    const int pry = magic_div(pr, pd.m_px);
-    const int py0 = pry * TH, px0 = (pr - pry * pd.patchesX) * TW;
+    const int bid = xcd_block_order();
+    HALO_PATCH_POS(BN, TH, TW, p, pd, bid);
 
     // ---- halo staging state (as conv3x3.hip) ----
     int pixoff[HI];
@@ -84,14 +70,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
         const int n = n0 + row;
         wvoff[i] = (n < p.N) ? (unsigned)(((size_t)n * p.ldw + ((lane & 7) ^ (row & 7)) * EPC) * sizeof(T)) : OOB;
     }
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in1, 0, p.bytes1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in2 ? p.in2 : p.in1), 0,
-                                                                         p.in2 ? p.bytes2 : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.bytesw, 0x00020000);
+    IGEMM_OPERAND_DESCRIPTORS(p);
 
     const int nchunks = p.Ctot / BKE;
-    const int ck0 = (nchunks * z) / p.splitk;
-    const int ck1 = (nchunks * (z + 1)) / p.splitk;
+    const KSlice slice = splitk_slice(nchunks, z, p.splitk);
+    const int ck0 = slice.k0, ck1 = slice.k1;
     const int S = (ck1 - ck0) * 9;
 
     u32x4 hr[HI];
@@ -99,28 +82,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
 #pragma unroll
     for (int j = 0; j < EPC; ++j) { sc[j] = 1.f; sh[j] = 0.f; }
 
-#define D3_LOAD_HALO(ck)                                                                            \
-    {                                                                                               \
-        const int c0_ = (ck) * BKE;                                                                 \
-        const bool first_ = c0_ < p.C1;                                                             \
-        const __amdgpu_buffer_rsrc_t rs_ = first_ ? rs1 : rs2;                                      \
-        const int ld_ = first_ ? p.ld1 : p.ld2;                                                     \
-        const int cofs_ = (first_ ? c0_ : c0_ - p.C1) + cpos * EPC;                                 \
-        _Pragma("unroll") for (int i = 0; i < HI; ++i) {                                            \
-            const unsigned off_ = (unsigned)(pixoff[i] * ld_ + cofs_) * (unsigned)sizeof(T);        \
-            hr[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_, pixoff[i] >= 0 ? off_ : OOB, 0, 0);  \
-        }                                                                                           \
-        if (FUSE) {                                                                                 \
-            const float* gs_ = p.gn_gamma + c0_ + cpos * EPC;                                       \
-            const float* gh_ = p.gn_beta + c0_ + cpos * EPC;                                        \
-            _Pragma("unroll") for (int j = 0; j < EPC; j += 4) {                                    \
-                const float4 a_ = *reinterpret_cast<const float4*>(gs_ + j);                        \
-                const float4 b_ = *reinterpret_cast<const float4*>(gh_ + j);                        \
-                sc[j] = a_.x; sc[j + 1] = a_.y; sc[j + 2] = a_.z; sc[j + 3] = a_.w;                 \
-                sh[j] = b_.x; sh[j + 1] = b_.y; sh[j + 2] = b_.z; sh[j + 3] = b_.w;                 \
-            }                                                                                       \
-        }                                                                                           \
-    }
 // normalise (FUSE) and write the staged chunk to the (single) halo buffer; all LDS traffic as asm
 #define D3_STORE_HALO(ck_)                                                                          \
     {                                                                                               \
@@ -131,13 +92,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
                 const unsigned ga_ = gstat_addr + __umulhi(cb_ + j, p.gn_magic) * 8u;               \
                 asm volatile("ds_read_b64 %0, %1" : "=v"(st_[j]) : "v"(ga_));                       \
             }                                                                                       \
-            c3_wait_lgkmcnt<0>();                                                                   \
+            wait_lgkmcnt<0>();                                                                      \
             __builtin_amdgcn_sched_barrier(0);                                                      \
-            _Pragma("unroll") for (int j = 0; j < EPC; ++j) {                                       \
-                const float s_ = st_[j].y * sc[j];                                                  \
-                sh[j] = sh[j] - st_[j].x * s_;                                                      \
-                sc[j] = s_;                                                                         \
-            }                                                                                       \
+            _Pragma("unroll") for (int j = 0; j < EPC; ++j) gn_fold_affine(st_[j], sc[j], sh[j]);   \
         }                                                                                           \
         _Pragma("unroll") for (int i = 0; i < HI; ++i) {                                            \
             if (haddr[i] != 0xffffffffu) {                                                          \
@@ -149,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
                 asm volatile("ds_write_b128 %0, %1" ::"v"(haddr[i]), "v"(v_) : "memory");           \
             }                                                                                       \
         }                                                                                           \
-        c3_wait_lgkmcnt<0>();                                                                       \
+        wait_lgkmcnt<0>();                                                                          \
     }
     // weight stream: (lck, ltap) = tile the next D3_DMA_W fetches; tile s goes to ring slot s % 3
     int lck = ck0, ltap = 0, lslot = 0;
@@ -172,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
 
     C3D_STAMP(1);
     if (S > 0) {
-        D3_LOAD_HALO(ck0);
+        HALO_LOAD_CHUNK(ck0);
         D3_DMA_W();              // the first two weight tiles fly while the group statistics are folded and the
         if (S > 1) D3_DMA_W();   // first halo chunk is normalised (the fold's plain LDS stores make the compiler drain
         if (FUSE) gn_fold_groups(p, b, gstat);   // them: everything requested so far lands together)
@@ -205,12 +162,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
             // weight tile s has landed once at most the next tile's LW loads of this wave are outstanding (the halo loads
             // of tap 0 are issued BEFORE that tile's DMA, so they are older and covered by the same wait)
             C3D_STAMP(16 + ((ck - ck0) * 9 + tap) * 3);
-            if (tap < 8 || next_chunk) c3_wait_vmcnt<LW>();
-            else c3_wait_vmcnt<0>();
+            if (tap < 8 || next_chunk) wait_vmcnt<LW>();
+            else wait_vmcnt<0>();
             C3D_STAMP(16 + ((ck - ck0) * 9 + tap) * 3 + 1);
             __builtin_amdgcn_s_barrier();   // this tap's tile (and at tap 0 the new halo) visible; ring slot (tap + 2) % 3 is free
             C3D_STAMP(16 + ((ck - ck0) * 9 + tap) * 3 + 2);
-            if (tap == 0 && next_chunk) D3_LOAD_HALO(ck + 1);
+            if (tap == 0 && next_chunk) HALO_LOAD_CHUNK(ck + 1);
             if (tap < 7 || next_chunk) D3_DMA_W();
             __builtin_amdgcn_sched_barrier(0);
             {
@@ -228,14 +185,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
 #pragma unroll
                 for (int j = 0; j < NI; ++j)
                     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[1][j]) : "v"(wf1), "n"(cur * kW_BYTES + j * 2048));
-                c3_wait_lgkmcnt<MI + NI>();
+                wait_lgkmcnt<MI + NI>();
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
 #pragma unroll
                     for (int j = 0; j < NI; ++j)
                         mma16<T>(__builtin_bit_cast(uint4, wf[0][j]), __builtin_bit_cast(uint4, af[0][i]), acc[i][j]);
-                c3_wait_lgkmcnt<0>();
+                wait_lgkmcnt<0>();
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
@@ -250,11 +207,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
             }
         }
     }
-#undef D3_LOAD_HALO
 #undef D3_STORE_HALO
 #undef D3_DMA_W
     C3D_STAMP(4);
-    c3_wait_vmcnt<0>();
+    wait_vmcnt<0>();
     __syncthreads();   // the LDS becomes the statistics scratch of the epilogue
     halo_tile_epilogue<T, BN>(p, acc, b, py0, px0, n0, z, reinterpret_cast<float*>(smem_raw));
     C3D_STAMP(5);
@@ -266,22 +222,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
 }
 
 template <typename T, int BN, bool FUSE>
-int launch_dma_one(const IgemmP& p0, hipStream_t s) {
-    IgemmP p = p0;
+int launch_dma_one(const IgemmP& p, hipStream_t s) {
     constexpr size_t lds = (size_t)(HPIX * 8 + 3 * BN * 8) * 16 + 32 * sizeof(float2);
-    auto kern = conv3x3_halo_dma_kernel<T, BN, FUSE>;
-    static std::atomic<uint64_t> attr_done{0};
-    if (int e = madm_raise_dynamic_lds(reinterpret_cast<const void*>(kern), (size_t)(lds), attr_done, "conv3x3 (LDS-DMA)")) return e;
-    const int patchesX = (p.OW + TW - 1) / TW, patchesY = (p.OH + TH - 1) / TH;
-    p.tilesN = (p.N + BN - 1) / BN;
-    dim3 grid((unsigned)(p.B * patchesX * patchesY * p.tilesN), 1, (unsigned)p.splitk);
-    PatchDecode pd;
-    if (!patch_decode_fill(pd, patchesX, patchesY, p.tilesN, (long long)grid.x)) {
-        madm_set_error("conv3x3 (LDS-DMA): grid of %u blocks too large for the reciprocal patch decode", grid.x);
-        return MADM_ERR_INVALID_ARG;
-    }
-    kern<<<grid, 256, lds, s>>>(p, pd);
-    return madm_check_launch("conv3x3_halo_dma_kernel");
+    return launch_halo_patches<conv3x3_halo_dma_kernel<T, BN, FUSE>, BN, TH, TW>(p, lds, s, "conv3x3 (LDS-DMA)", "conv3x3_halo_dma_kernel");
 }
 
 }  // namespace

@@ -38,11 +38,6 @@ __device__ unsigned long long g_h16_stamps[8192 + 4 * 8192];
 #define H16_STAMP(i_)
 #endif
 
-#if defined(__HIP_DEVICE_COMPILE__)
-template <int N> __device__ __forceinline__ void h16_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void h16_wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-#endif
-
 // GroupNorm affine + activation of one 16-byte chunk.  f16: the affine runs as packed f16 FMAs on the stored pairs and the
 // SiLU as f16 exp / rcp (4 instructions per element instead of ~11; the result is rounded to f16 storage either way).
 template <typename T, int EPC>
@@ -214,7 +209,7 @@ __device__ __forceinline__ void h16_epilogue_lds(const IgemmP& p, f32x4 (&acc)[M
             if (!full && (oy >= p.OH || ox >= p.OW || n >= p.N)) off = 0x80000000u;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsr, lds3 + (wave * 16 + t) * 1024, 16, off, 0, 0, 0);
         }
-        h16_wait_vmcnt<0>();
+        wait_vmcnt<0>();
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
@@ -330,11 +325,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h16_kernel(const IgemmP p, con
     const int frow = lane & 15, fg = lane >> 4;
     const int z = blockIdx.z;
 
-    int bid = blockIdx.x;   // XCD-aware order (see igemm.hip)
-    {
-        const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = bid & 7, i = bid >> 3;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
+    const int bid = xcd_block_order();
 #ifdef H16_STAMPS
     const bool stamp_on = blockIdx.x == gridDim.x / 2 + 1 && blockIdx.z == 0 && tid == 0;
     int stamp_i = 8;
@@ -349,12 +340,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h16_kernel(const IgemmP p, con
         g_h16_stamps[8192 + 4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((31 << 11) | 6);
     }
 #endif
-    const int tm = magic_div(bid, pd.m_tilesN), tn = bid - tm * p.tilesN;
-    const int n0 = tn * BN;
-    const int b = magic_div(tm, pd.m_ppi);
-    const int pr = tm - b * pd.patchesPerImg;
-    const int pry = magic_div(pr, pd.m_px);
-    const int py0 = pry * H16_T, px0 = (pr - pry * pd.patchesX) * H16_T;
+    HALO_PATCH_POS(BN, H16_T, H16_T, p, pd, bid);
 
     // ---- halo DMA state: piece q = wave + 4 i; lane l lands LDS slot (pixel 8 q + (l >> 3), 16-byte slot l & 7), which
     //      must hold global chunk (l & 7) ^ (hx & 7) of that pixel.  pk = pixel offset * 8 + global chunk, -1 = zeros ----
@@ -365,15 +351,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h16_kernel(const IgemmP p, con
     const int wrow0 = wave * LW * 8 + hl;
     const unsigned wv0 = (unsigned)(((size_t)(n0 + wrow0) * p.ldw + (cl ^ hl) * EPC) * sizeof(T));
     const unsigned wvstep = (unsigned)__builtin_amdgcn_readfirstlane((int)((size_t)8 * p.ldw * sizeof(T)));
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in1, 0, p.bytes1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in2 ? p.in2 : p.in1), 0,
-                                                                         p.in2 ? p.bytes2 : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.bytesw, 0x00020000);
+    IGEMM_OPERAND_DESCRIPTORS(p);
 
     const int ush = __builtin_amdgcn_readfirstlane(p.upsample ? 1 : 0);   // (never together with FUSE: the launcher checks)
     const int nchunks = p.Ctot / BKE;
-    const int ck0 = (nchunks * z) / p.splitk;
-    const int ck1 = (nchunks * (z + 1)) / p.splitk;
+    const KSlice slice = splitk_slice(nchunks, z, p.splitk);
+    const int ck0 = slice.k0, ck1 = slice.k1;
 
 #define H16_DMA_HALO(ck)                                                                                \
     {                                                                                                   \
@@ -431,12 +414,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h16_kernel(const IgemmP p, con
                 sc_[j] = a_.x; sc_[j + 1] = a_.y; sc_[j + 2] = a_.z; sc_[j + 3] = a_.w;                 \
                 sh_[j] = b_.x; sh_[j + 1] = b_.y; sh_[j + 2] = b_.z; sh_[j + 3] = b_.w;                 \
             }                                                                                           \
-            h16_wait_lgkmcnt<0>();                                                                      \
-            _Pragma("unroll") for (int j = 0; j < EPC; ++j) {                                           \
-                const float s_ = st_[j].y * sc_[j];                                                     \
-                sh_[j] = sh_[j] - st_[j].x * s_;                                                        \
-                sc_[j] = s_;                                                                            \
-            }                                                                                           \
+            wait_lgkmcnt<0>();                                                                          \
+            _Pragma("unroll") for (int j = 0; j < EPC; ++j) gn_fold_affine(st_[j], sc_[j], sh_[j]);     \
         }                                                                                               \
         H16_STAMP(6);                                                                                   \
         int tp_ = tid >> 3;                                                                             \
@@ -489,7 +468,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h16_kernel(const IgemmP p, con
     for (int ck = ck0; ck < ck1; ++ck) {
         // ---- the chunk's halo has been requested: land it, normalise it ----
         H16_STAMP(stamp_i); 
-        h16_wait_vmcnt<0>();
+        wait_vmcnt<0>();
         __syncthreads();
         H16_STAMP(stamp_i + 1);
         if (FUSE) {
@@ -508,7 +487,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h16_kernel(const IgemmP p, con
         for (int tap = 0; tap < 9; ++tap) {
             const bool more = (tap < 8) || (ck + 1 < ck1);
             if (tap > 0) {                    // tap 0's tile was waited for together with the halo
-                h16_wait_vmcnt<0>();
+                wait_vmcnt<0>();
                 __builtin_amdgcn_s_barrier();  // this tap's tile visible; the other slot (read by tap - 1) is free
             }
             H16_STAMP(stamp_i);
@@ -530,7 +509,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h16_kernel(const IgemmP p, con
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(af[1][i]) : "v"(a0), "n"((r_ + 4 + i) * ROWB));
-                h16_wait_lgkmcnt<4>();
+                wait_lgkmcnt<4>();
                 __builtin_amdgcn_sched_barrier(0);
                 H16_STAMP(stamp_i + 2);
 #pragma unroll
@@ -546,7 +525,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h16_kernel(const IgemmP p, con
 #pragma unroll
                 for (int j = 0; j < NI; ++j)
                     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[1][j]) : "v"(w1), "n"(j * 2048));
-                h16_wait_lgkmcnt<4 + NI>();
+                wait_lgkmcnt<4 + NI>();
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -557,14 +536,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h16_kernel(const IgemmP p, con
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(af[1][i]) : "v"(a1), "n"((r_ + 4 + i) * ROWB));
-                h16_wait_lgkmcnt<4>();
+                wait_lgkmcnt<4>();
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < NI; ++j)
                         mma16<T>(__builtin_bit_cast(uint4, wf[1][j]), __builtin_bit_cast(uint4, af[0][i]), acc[i][j]);
-                h16_wait_lgkmcnt<0>();
+                wait_lgkmcnt<0>();
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -588,7 +567,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h16_kernel(const IgemmP p, con
 #undef H16_TRANSFORM
 #undef H16_DMA_W
     H16_STAMP(4);
-    h16_wait_vmcnt<0>();
+    wait_vmcnt<0>();
     __syncthreads();   // the LDS becomes the statistics scratch of the epilogue
     // WIDE (chosen by the launcher): 16-bit outputs without split-K / GEGLU whose rows keep 16-byte alignment
     // the epilogue is VALU work on the block's critical path like the GroupNorm pass: raised issue priority beside the partner
@@ -615,38 +594,14 @@ extern "C" int madm_debug_read_h16_stamps(unsigned long long* host, int n) {
 namespace {
 
 template <typename T, int BN, bool FUSE, bool WIDE, bool SK = false>
-int launch_h16_one(const IgemmP& p0, hipStream_t s) {
-    IgemmP p = p0;
+int launch_h16_one(const IgemmP& p, hipStream_t s) {
     constexpr size_t lds0 = (size_t)((H16_PIX + 7) / 8) * 1024 + 2 * (size_t)BN * 128 + 32 * sizeof(float2);
     // experiment (MADM_EXP_H16_LDS=<bytes>): ask for more LDS than the kernel uses, e.g. 90112 -> ONE workgroup per CU, the
     // rest of the CU stays free for the workgroups of kernels on other streams (staged pipeline)
     static const size_t lds_exp = [] { const char* e = getenv("MADM_EXP_H16_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
     const size_t lds = lds_exp > lds0 ? lds_exp : lds0;
-    auto kern = conv3x3_h16_kernel<T, BN, FUSE, WIDE, SK>;
-    // the attribute is per device: one bit per device id, set once (atomic: host threads may launch concurrently)
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)(lds > 64 * 1024 ? lds : 64 * 1024));
-        if (e != hipSuccess) {
-            madm_set_error("conv3x3 (16 x 16 patches): cannot raise dynamic LDS to %zu: %s", lds, hipGetErrorString(e));
-            return MADM_ERR_LAUNCH;
-        }
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    const int patchesX = (p.OW + H16_T - 1) / H16_T, patchesY = (p.OH + H16_T - 1) / H16_T;
-    p.tilesN = (p.N + BN - 1) / BN;
-    dim3 grid((unsigned)(p.B * patchesX * patchesY * p.tilesN), 1, (unsigned)p.splitk);
-    PatchDecode pd;
-    if (!patch_decode_fill(pd, patchesX, patchesY, p.tilesN, (long long)grid.x)) {
-        madm_set_error("conv3x3 (16 x 16 patches): grid of %u blocks too large for the reciprocal patch decode", grid.x);
-        return MADM_ERR_INVALID_ARG;
-    }
-    kern<<<grid, 256, lds, s>>>(p, pd);
-    return madm_check_launch("conv3x3_h16_kernel");
+    return launch_halo_patches<conv3x3_h16_kernel<T, BN, FUSE, WIDE, SK>, BN, H16_T, H16_T>(p, lds, s, "conv3x3 (16 x 16 patches)",
+                                                                                            "conv3x3_h16_kernel");
 }
 
 }  // namespace

@@ -8,12 +8,10 @@
 // t+1 are issued before the MFMAs of tile t and written to the other buffer after them; one
 // barrier per K-tile.  The MFMA is issued as D = W_frag x A_frag so that every lane ends up with
 // 4 CONSECUTIVE output channels of one pixel: 8/16-byte stores, vector bias / residual loads.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
 #include <atomic>
-#include "igemm_common.hpp"
+#include "conv_plan.hpp"
+
+using namespace conv_plan;
 
 namespace {
 #ifdef GLDS_STAMPS   // tools/exp/stamps_reg.py: block-level timeline of one block of the register-staged kernel
@@ -203,14 +201,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void igemm_ker
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     REG_BSTAMP(0);
     const int wm = wave >> 1, wn = wave & 1;
-    // XCD-aware order: blocks b and b+8 share an XCD (round-robin dispatch), so give every XCD a contiguous
-    // range of tiles -- neighbouring output rows re-read the same input lines / weight panels from ITS L2.
-    // (placement only changes speed; the remap is a bijection for any grid size)
-    int bid = blockIdx.x;
-    {
-        const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = bid & 7, i = bid >> 3;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
+    const int bid = xcd_block_order();
     const int tn = bid % p.tilesN, tm = bid / p.tilesN;
     const int m0 = tm * BM, n0 = tn * BN;
     const int z = blockIdx.z;
@@ -226,15 +217,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void igemm_ker
     for (int i = 0; i < RA; ++i) {
         const int m = m0 + lrow + 32 * i;
         if (m < p.M) {
-            if constexpr (LIN) {
-                a_b[i] = m; a_iy[i] = 0; a_ix[i] = 0;   // a_b = input row, a_iy >= 0 marks it valid
-            } else {
-                const int b = m / OHW;
-                const int r = m - b * OHW;
-                const int oy = r / p.OW;
-                const int ox = r - oy * p.OW;
-                a_b[i] = b * p.IH; a_iy[i] = oy * p.stride - p.pad_t; a_ix[i] = ox * p.stride - p.pad_l;
-            }
+            IGEMM_ROW_DECODE(LIN, p, m, OHW, a_b[i], a_iy[i], a_ix[i])
         } else {
             a_b[i] = 0; a_iy[i] = -(1 << 24); a_ix[i] = 0;  // never in range
         }
@@ -245,32 +228,16 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void igemm_ker
         const int n = n0 + lrow + 32 * i;
         wvoff[i] = (n < p.N) ? (unsigned)(((size_t)n * p.ldw + chunk * EPC) * sizeof(T)) : OOB;
     }
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in1, 0, p.bytes1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in2 ? p.in2 : p.in1), 0,
-                                                                         p.in2 ? p.bytes2 : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.bytesw, 0x00020000);
+    IGEMM_OPERAND_DESCRIPTORS(p);
 
     // (integer divisions by run-time values cost ~150 clocks each on this VALU and sit in front of the first load: the
     // common cases -- no split-K, linear layers -- take none)
     int kt0 = 0, kt1 = p.nk;
     if (p.splitk > 1) {
-        kt0 = (p.nk * z) / p.splitk;
-        kt1 = (p.nk * (z + 1)) / p.splitk;
+        const KSlice slice = splitk_slice(p.nk, z, p.splitk);
+        kt0 = slice.k0; kt1 = slice.k1;
     }
-    // tap state of the NEXT tile to load
-    int c0, tr, ts;
-    if constexpr (LIN) {
-        c0 = kt0 * BKE; tr = 0; ts = 0;      // one tap: k = channel
-    } else {
-        const int kbase = kt0 * BKE;
-        const int tap = kbase / p.Ctot;
-        c0 = kbase - tap * p.Ctot;
-        tr = tap / p.KW;
-        ts = tap - tr * p.KW;
-    }
-    const int IHe = p.upsample ? 2 * p.IH : p.IH;
-    const int IWe = p.upsample ? 2 * p.IW : p.IW;
-    const int ush = p.upsample ? 1 : 0;
+    IGEMM_TAP_STATE(LIN, p, kt0 * BKE);   // (c0, tr, ts): of the NEXT tile to load
 
     u32x4 ra[NST][RA], rb[NST][RB];   // NST register stages: the global loads run NST K-tiles ahead of the MFMAs
 
@@ -387,13 +354,8 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void igemm_ker
 // fetches global chunk p ^ (r & 7)), so the LDS image -- and the fragment reads -- are those of igemm_kernel.
 // Per K-tile: counted s_waitcnt vmcnt (only this tile's loads must have landed) -> one barrier (tile visible to every
 // wave, previous slot free) -> issue the loads of tile t + NS - 1 into that slot -> ds_read + MFMA.
-#define GLDS_ASM(...) asm volatile(__VA_ARGS__)
 #ifdef GLDS_STAMPS
 __device__ unsigned long long g_glds_stamps[2048];
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-template <int N> __device__ __forceinline__ void wait_vmcnt() { GLDS_ASM("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void wait_lgkmcnt() { GLDS_ASM("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
 #endif
 
 // LIN: 1x1 / stride 1 / no padding / no upsampling (every linear layer and 1x1 conv): output row m reads input row m, so
@@ -425,11 +387,7 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? (NS == 2 ? 2 : 1) : (NS
 #define GLDS_BSTAMP(k_)
 #endif
     GLDS_BSTAMP(0);
-    int bid = blockIdx.x;   // XCD-aware order, see igemm_kernel
-    {
-        const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = bid & 7, i = bid >> 3;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
+    const int bid = xcd_block_order();
     const int tn = bid % p.tilesN, tm = bid / p.tilesN;
     const int m0 = tm * BM, n0 = tn * BN;
     const int z = blockIdx.z;
@@ -448,45 +406,22 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? (NS == 2 ? 2 : 1) : (NS
         if (row < BM) {
             const int m = m0 + row;
             if (m < p.M) {
-                if constexpr (LIN) {
-                    a_b[i] = m; a_iy[i] = 0;   // a_b = input row, a_iy >= 0 marks it valid
-                } else {
-                    const int b = m / OHW;
-                    const int r = m - b * OHW;
-                    const int oy = r / p.OW;
-                    const int ox = r - oy * p.OW;
-                    a_b[i] = b * p.IH; a_iy[i] = oy * p.stride - p.pad_t; a_ix[i] = ox * p.stride - p.pad_l;
-                }
+                IGEMM_ROW_DECODE(LIN, p, m, OHW, a_b[i], a_iy[i], a_ix[i])
             }
         } else {
             const int n = n0 + row - BM;
             if (n < p.N) wvoff[i] = (unsigned)(((size_t)n * p.ldw + swz[i]) * sizeof(T));
         }
     }
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in1, 0, p.bytes1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in2 ? p.in2 : p.in1), 0,
-                                                                         p.in2 ? p.bytes2 : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.bytesw, 0x00020000);
+    IGEMM_OPERAND_DESCRIPTORS(p);
 
     int kt0 = 0, kt1 = p.nk;     // (no run-time divisions in front of the first load in the common cases, see igemm_kernel)
     if (p.splitk > 1) {
-        kt0 = (p.nk * z) / p.splitk;
-        kt1 = (p.nk * (z + 1)) / p.splitk;
+        const KSlice slice = splitk_slice(p.nk, z, p.splitk);
+        kt0 = slice.k0; kt1 = slice.k1;
     }
     const int nt = kt1 - kt0;
-    int c0, tr, ts;   // tap state of the NEXT tile to load
-    if constexpr (LIN) {
-        c0 = kt0 * BKE; tr = 0; ts = 0;
-    } else {
-        const int kbase = kt0 * BKE;
-        const int tap = kbase / p.Ctot;
-        c0 = kbase - tap * p.Ctot;
-        tr = tap / p.KW;
-        ts = tap - tr * p.KW;
-    }
-    const int IHe = p.upsample ? 2 * p.IH : p.IH;
-    const int IWe = p.upsample ? 2 * p.IW : p.IW;
-    const int ush = p.upsample ? 1 : 0;
+    IGEMM_TAP_STATE(LIN, p, kt0 * BKE);   // (c0, tr, ts): of the NEXT tile to load
     lds_char* const lds0 = (lds_char*)gsmem;
 
 #define GLDS_LOAD_TILE(kt, slot)                                                                                 \
@@ -600,9 +535,9 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? (NS == 2 ? 2 : 1) : (NS
             _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                                   \
                 const unsigned pa = aA[kk] + (CUR) * (TILE_U4 * 16), pb = aB[kk] + (CUR) * (TILE_U4 * 16);       \
                 _Pragma("unroll") for (int i = 0; i < MI; ++i)                                                   \
-                    GLDS_ASM("ds_read_b128 %0, %1 offset:%2" : "=v"(af[kk][i]) : "v"(pa), "n"(i * 2048));         \
+                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(af[kk][i]) : "v"(pa), "n"(i * 2048));    \
                 _Pragma("unroll") for (int j = 0; j < NI; ++j)                                                   \
-                    GLDS_ASM("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[kk][j]) : "v"(pb), "n"(j * 2048));         \
+                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[kk][j]) : "v"(pb), "n"(j * 2048));    \
             }                                                                                                    \
             wait_lgkmcnt<MI + NI>();                                                                             \
             __builtin_amdgcn_sched_barrier(0);                                                                   \
@@ -729,7 +664,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const IgemmP p) {
 // before it (L2-resident slabs): a latency kernel, so 16 waves per workgroup with four slab loads in flight each.
 struct PostGn { const float* gamma; const float* beta; int G; float eps; int act; };
 constexpr int PGN_THREADS = 1024;
-constexpr size_t PGN_MAX_LDS = 96 * 1024;
 
 // V = floats per unit (4 when the group's channel count allows 16-byte accesses, else 2).
 template <typename T, int V>
@@ -807,282 +741,6 @@ __global__ __launch_bounds__(PGN_THREADS) void splitk_groupnorm_kernel(const Ige
     }
 }
 
-// LDS of one (image, group) workgroup of splitk_groupnorm_kernel
-inline size_t post_gn_lds(int HW, int N, int G) { return (size_t)HW * (size_t)(N / G) * sizeof(float); }
-
-// The tile codes of madm_conv2d_plan.tile, the tuned tables and madm_debug_set_conv_tile; the names are bench.py's kernel classes.
-// IGEMM = register-staged implicit GEMM, `slots` deep (6: for latency-bound small-M GEMMs streaming cold weights); GLDS = fed by
-// LDS-DMA through a ring of `slots` stages (+ the 3 KB constant stash of every instantiation: 11 and 17 = 51 KB, three blocks per
-// CU; 16 = 35 KB, four, whose prologues and epilogues cover each other on short-K layers; 14 / 15 = 99 / 67 KB, 8 KB of operands
-// per MFLOP instead of 11 (128x64) / 31 (64x64): few fat workgroups for launches whose neighbours are other streams' kernels);
-// HALO / HALO_DMA = 3x3 conv on 8 x 16-pixel halo patches, weights through registers / LDS-DMA; H16 = 16 x 16-pixel patches, all
-// by LDS-DMA, folds a 2x upsample (maps >= 16 x 16); APANEL = A-stationary linear layer (BM / BN only feed the split-K heuristic)
-enum TileFamily { IGEMM, GLDS, HALO, HALO_DMA, H16, APANEL };
-struct Tile { int code, bm, bn; TileFamily family; int slots; const char* name; };
-constexpr Tile g_tiles[] = {
-    {1, 128, 128, IGEMM, 2, "igemm_128x128"},        {2, 128, 64, IGEMM, 3, "igemm_128x64"},          {3, 64, 64, IGEMM, 4, "igemm_64x64"},
-    {4, 128, 128, HALO, 0, "conv3x3_halo_x128"},     {5, 128, 64, HALO, 0, "conv3x3_halo_x64"},       {6, 64, 64, IGEMM, 8, "igemm_64x64d"},
-    {7, 64, 64, GLDS, 4, "igemm_glds_64x64"},        {8, 128, 64, GLDS, 3, "igemm_glds_128x64"},      {9, 128, 128, HALO_DMA, 0, "conv3x3_halo_dma_x128"},
-    {10, 128, 64, HALO_DMA, 0, "conv3x3_halo_dma_x64"}, {11, 64, 64, GLDS, 3, "igemm_glds_64x64s"},   {12, 256, 128, H16, 0, "conv3x3_h16_x128"},
-    {13, 64, 64, APANEL, 0, "igemm_apanel"},         {14, 128, 128, GLDS, 3, "igemm_glds_128x128"},   {15, 128, 128, GLDS, 2, "igemm_glds_128x128d"},
-    {16, 64, 64, GLDS, 2, "igemm_glds_64x64d"},      {17, 128, 64, GLDS, 2, "igemm_glds_128x64d"}};
-constexpr int N_TILES = sizeof g_tiles / sizeof g_tiles[0];
-inline const Tile* tile_info(int t) { return t >= 1 && t <= N_TILES && g_tiles[t - 1].code == t ? &g_tiles[t - 1] : nullptr; }
-inline bool is_igemm_tile(int t) { const Tile* i = tile_info(t); return i && (i->family == IGEMM || i->family == GLDS); }
-inline bool is_halo_tile(int t) { const Tile* i = tile_info(t); return i && i->family >= HALO && i->family <= H16; }
-int g_tile_override = 0;  // 0 = tuned table then heuristic; -1 = heuristic only; 1..N_TILES = forced tile code
-// tile 13 (igemm_apanel.hip): plain linear layer, one source, whole rows resident: no split-K, no residual / time row /
-// fused output statistics (its epilogue touches no global memory but the stores)
-inline bool apanel_eligible(const madm_conv2d_args* a) {
-    return a->KH == 1 && a->KW == 1 && a->stride == 1 && a->pad_t == 0 && a->pad_l == 0 && !a->upsample && a->C2 == 0 &&
-           a->OH == a->IH && a->OW == a->IW && a->splitk <= 1 && !a->stats && !a->residual && !a->rowvec && !a->gn_sums1 &&
-           igemm_apanel_bm(a->C1, (int)madm_esize(a->dtype)) > 0 &&
-           // its stores go through a buffer descriptor with 32-bit offsets (0x80000000 = "drop this lane")
-           (size_t)a->B * a->OH * a->OW * (size_t)a->ldo * (a->out_f32 ? 4 : madm_esize(a->dtype)) < 0x80000000ull;
-}
-
-// Launch configurations measured on MI355X by tools/tune_insitu.py for the layer shapes of the SD-v1-4
-// feature extractor at bs=2, 512x512 (any other shape falls back to the heuristics below).
-// variant: 0 = plain, 1 = GroupNorm fused into the halo load, 2 = nearest-2x upsample gather, 3 = stride 2 (a downsample
-// conv shares M, N, K with a stride-1 conv of the next level: 8 x 8 x 1280 of the UNet; without a row of its own it takes
-// the plain row)
-struct Tuned { int dtype, M, N, K, KH, variant, tile, splitk; };
-inline int variant_of(const madm_conv2d_args* a) { return a->gn_sums1 ? 1 : (a->upsample ? 2 : (a->stride == 2 ? 3 : 0)); }
-const Tuned g_tuned[] = {
-#include "igemm_tuned.inc"
-    {-1, 0, 0, 0, 0, 0, 0, 0}};
-// The table above is tuned for THROUGHPUT: rows chosen with three launches of the layer side by side (tools/tune_concurrent.py), the
-// neighbours a launch has under the runners of madm_amd/pipeline.py.  A synchronous caller -- the reference's loop calling forward()
-// with one batch in flight -- wants the choice that is fastest ALONE on an idle chip: more split-K, the tile that fills 256 CUs by
-// itself.  Profile 1 (madm_set_tuning_profile; ops.tuning_profile("latency")) puts these rows in front of the table; a shape without
-// one keeps its throughput row.
-const Tuned g_tuned_latency[] = {
-#include "igemm_tuned_latency.inc"
-    {-1, 0, 0, 0, 0, 0, 0, 0}};
-std::atomic<int> g_tuning_profile{0};
-
-// Run-time rows in front of the compiled-in table (A/B runs of tools/tune_concurrent.py without a rebuild): the file named
-// by MADM_TUNED_FILE holds one "dtype M N K KH variant tile splitk" row per line ('#' starts a comment); read once.
-const std::vector<Tuned>& tuned_overrides() {
-    static const std::vector<Tuned> rows = [] {
-        std::vector<Tuned> v;
-        const char* path = getenv("MADM_TUNED_FILE");
-        if (!path || !*path) return v;
-        FILE* f = fopen(path, "r");
-        if (!f) { fprintf(stderr, "madm: MADM_TUNED_FILE=%s cannot be opened\n", path); return v; }
-        char line[256];
-        while (fgets(line, sizeof line, f)) {
-            Tuned t;
-            if (line[0] == '#') continue;
-            if (sscanf(line, "%d %d %d %d %d %d %d %d", &t.dtype, &t.M, &t.N, &t.K, &t.KH, &t.variant, &t.tile, &t.splitk) != 8)
-                continue;
-            // a row with an unknown tile code would fall through to the default igemm launch unnoticed: refuse it loudly
-            if (!tile_info(t.tile) || t.splitk < 1 || t.variant < 0 || t.variant > 3 || !madm_dtype_ok(t.dtype)) {
-                fprintf(stderr, "madm: MADM_TUNED_FILE=%s: row ignored (tile 1..%d, splitk >= 1, variant 0..3): %s", path, N_TILES, line);
-                continue;
-            }
-            v.push_back(t);
-        }
-        fclose(f);
-        return v;
-    }();
-    return rows;
-}
-
-// One conv2d request while it is being decided: the arguments as they stand at this stage of the decision, the GEMM they
-// describe, and the two process-wide knobs, read ONCE -- every tile / split-K question of one launch is answered from here.
-struct Request {
-    const madm_conv2d_args* a;
-    int M, K;                     // B OH OW, KH KW (C1 + C2)
-    int tile_override, profile;   // g_tile_override, g_tuning_profile
-    explicit Request(const madm_conv2d_args* args)
-        : a(args), M(args->B * args->OH * args->OW), K(args->KH * args->KW * (args->C1 + args->C2)),
-          tile_override(g_tile_override), profile(g_tuning_profile.load(std::memory_order_relaxed)) {}
-    int k_steps() const { return K / (8 * madm_epc(a->dtype)); }
-    int channel_chunks() const { return (a->C1 + a->C2) / (8 * madm_epc(a->dtype)); }
-    // the table row of this shape under `variant`: run-time rows, then the latency rows under profile 1, then the throughput table
-    const Tuned* row(int variant) const {
-        if (tile_override != 0) return nullptr;
-        const int dt = a->dtype == MADM_F16 ? MADM_BF16 : a->dtype;   // same kernels, same instruction rate: the bf16 table serves both
-        auto hit = [&](const Tuned& t) { return t.dtype == dt && t.M == M && t.N == a->N && t.K == K && t.KH == a->KH && t.variant == variant; };
-        for (const Tuned& t : tuned_overrides())
-            if (hit(t)) return &t;
-        for (const Tuned* t = g_tuned_latency; profile == 1 && t->dtype >= 0; ++t)
-            if (hit(*t)) return t;
-        for (const Tuned* t = g_tuned; t->dtype >= 0; ++t)
-            if (hit(*t)) return t;
-        return variant == 3 ? row(0) : nullptr;
-    }
-};
-
-int heuristic_tile(int M, int N, int K) {
-    auto tiles = [&](int bm, int bn) { return (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-    // shapes without a tuned entry (the segmentation head, the training step's gradients, other batch sizes): the
-    // register-staged 128 x 128 tile never wins a tuned entry and loses 25 .. 40 % on the head's M = 524 288 GEMMs
-    // (M524288: N256 K1024 851 us vs 612 (tile 8) / 630 (tile 2); N1024 K256 1447 vs 892 (tile 2); MI355X, f16)
-    if (M >= 128 && tiles(128, 64) >= 256) return K >= 1024 ? 8 : 2;
-    return 3;
-}
-
-// narrowest map the halo kernels take (env MADM_HALO_MIN_W for A/B runs): an 8-wide map wastes half of every 8 x 16 patch,
-// but lets the 8 x 8 UNet level fuse its GroupNorm
-int halo_min_width() {
-    static const int w = [] { const char* e = getenv("MADM_HALO_MIN_W"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : v; }();
-    return w;
-}
-
-// the LDS halo-tile kernel (conv3x3.hip) handles 3x3 / stride 1 / pad 1 convs on maps of at least one patch
-bool halo_eligible(const madm_conv2d_args* a) {
-    return a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad_t == 1 && a->pad_l == 1 && !a->upsample &&
-           a->OH == a->IH && a->OW == a->IW && a->OH >= 8 && a->OW >= halo_min_width() && a->epilogue != MADM_EPI_GEGLU;
-}
-
-int pick_tile_raw(const Request& r) {
-    const madm_conv2d_args* a = r.a;
-    const int forced = r.tile_override;
-    const bool halo_ok = halo_eligible(a);
-    const int halo_default = (a->N % 128 == 0 || a->N >= 512) ? 4 : 5;
-    if (a->gn_sums1) {   // fused GroupNorm exists only in the halo kernels
-        if (is_halo_tile(forced)) return forced;
-        if (const Tuned* t = r.row(variant_of(a)))
-            if (is_halo_tile(t->tile)) return t->tile;
-        return halo_default;
-    }
-    if (is_igemm_tile(forced) || (is_halo_tile(forced) && halo_ok))
-        return forced;   // (13 = the A-stationary kernel is handled by pick_tile; ineligible launches fall through)
-    if (const Tuned* t = r.row(variant_of(a)))
-        if (is_igemm_tile(t->tile) || halo_ok) return t->tile;
-    if (halo_ok && r.M >= 2048) return halo_default;
-    return heuristic_tile(r.M, a->N, r.K);
-}
-
-// the 16 x 16-patch kernel pays where it fills the chip: at least ~0.75 rounds of its 256-pixel x 128-channel blocks
-// (measured against tile 9 on MI355X, bf16 / f16: +12 .. 23 % on the 512^2 .. 128^2 maps of the VAE, 0.6 x on an 8192-pixel map)
-bool h16_pays(const madm_conv2d_args* a) {
-    static const int off = [] { const char* e = getenv("MADM_NO_H16"); return e ? atoi(e) : 0; }();
-    if (off || a->OH < 16 || a->OW < 16 || a->N < 128) return false;
-    const long long blocks = (long long)a->B * ((a->OH + 15) / 16) * ((a->OW + 15) / 16) * ((a->N + 127) / 128);
-    return blocks >= 384;
-}
-
-// nearest-2x upsample + 3x3 conv (Upsample2D of the VAE decoder / UNet): only the 16 x 16-patch kernel folds the
-// upsample into its halo gather (igemm 128x64 on the 256-channel 512 x 512 layer: 456 us, this kernel: see DESIGN.md)
-bool h16_upsample_eligible(const madm_conv2d_args* a) {
-    return a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad_t == 1 && a->pad_l == 1 && a->upsample &&
-           a->OH == 2 * a->IH && a->OW == 2 * a->IW && !a->gn_sums1 && a->epilogue != MADM_EPI_GEGLU && a->OH >= 16 &&
-           a->OW >= 16;
-}
-
-int pick_tile(const Request& r) {
-    const madm_conv2d_args* a = r.a;
-    if (apanel_eligible(a)) {   // (K = C1, KH = 1, variant 0)
-        if (r.tile_override == 13) return 13;
-        if (const Tuned* t = r.row(0))
-            if (t->tile == 13) return 13;
-    }
-    if (h16_upsample_eligible(a)) {
-        // a table row decides (variant 2; the side-by-side tuner put the UNet's upsample convs here although their grids
-        // are far below a round of workgroups), h16_pays() where there is none; no row is looked up under a tile override
-        const Tuned* t = r.row(2);
-        if (r.tile_override == 12 || (t ? t->tile == 12 : (r.tile_override == 0 && h16_pays(a)))) return 12;
-    }
-    const int t = pick_tile_raw(r);
-    if (t == 12 && (a->OH < 16 || a->OW < 16)) return 9;   // the 16 x 16-patch kernel needs a map of at least one patch
-    if ((t == 4 || t == 9) && r.tile_override == 0 && h16_pays(a)) return 12;
-    return t;
-}
-
-// split-K for the 256 CUs of MI355X where the request leaves it to the library: the row's if its tile is the one chosen, else about two rounds
-int suggest_splitk(const Request& r) {
-    const int chosen = pick_tile(r), nk = r.k_steps();
-    if (const Tuned* t = r.row(variant_of(r.a)))
-        if (t->tile == chosen) return t->splitk;
-    const Tile* ti = tile_info(chosen);
-    const long long tiles = (long long)((r.M + ti->bm - 1) / ti->bm) * ((r.a->N + ti->bn - 1) / ti->bn);
-    if (tiles >= 192 || nk < 8) return 1;
-    return (int)std::max(1LL, std::min({(512 + tiles - 1) / tiles, nk / 4LL, 32LL}));
-}
-
-inline size_t splitk_workspace_bytes(int sk, const Request& r) { return sk > 1 ? (size_t)sk * (size_t)r.M * (size_t)r.a->N * sizeof(float) : 0; }
-
-// the arguments taken as they stand: the tile madm_conv2d_fwd launches and the split-K its kernels run with (at least one K step
-// per slice; the halo kernels split K by whole channel chunks)
-void resolve(const Request& r, madm_conv2d_plan& pl) {
-    pl.tile = pick_tile(r);
-    pl.splitk = r.a->splitk;
-    pl.splitk_eff = std::min(pl.splitk, r.k_steps());
-    if (is_halo_tile(pl.tile)) pl.splitk_eff = std::min(pl.splitk_eff, r.channel_chunks());
-    pl.splitk_eff = std::max(pl.splitk_eff, 1);
-    pl.workspace_bytes = splitk_workspace_bytes(pl.splitk, r);
-}
-
-// can the split-K reduction of this launch apply the consumer's GroupNorm (pn_groups)?
-bool post_gn_fits(const madm_conv2d_args* a, int splitk_eff) {
-    if (splitk_eff <= 1 || a->pn_groups <= 0 || a->N <= 0 || a->N % a->pn_groups) return false;
-    if (a->epilogue != MADM_EPI_NONE || a->residual || a->stats || a->out_f32 || a->ln_colsum) return false;
-    return (a->N / a->pn_groups) % 2 == 0 && post_gn_lds(a->OH * a->OW, a->N, a->pn_groups) <= PGN_MAX_LDS;
-}
-
-int fill_params(const Request& r, IgemmP& p) {
-    const madm_conv2d_args* a = r.a;
-    const int bke = (8 * madm_epc(a->dtype));
-    MADM_REQUIRE(a->in1 && a->w && a->out, "conv2d: null tensor pointer");
-    MADM_REQUIRE(a->C1 > 0 && a->C1 % bke == 0, "conv2d: C1=%d must be a positive multiple of %d", a->C1, bke);
-    MADM_REQUIRE(a->C2 >= 0 && a->C2 % bke == 0, "conv2d: C2=%d must be a multiple of %d", a->C2, bke);
-    MADM_REQUIRE(a->C2 == 0 || a->in2, "conv2d: C2>0 needs in2");
-    MADM_REQUIRE(a->B > 0 && a->IH > 0 && a->IW > 0 && a->OH > 0 && a->OW > 0, "conv2d: bad dims");
-    MADM_REQUIRE(a->KH > 0 && a->KW > 0 && a->stride > 0, "conv2d: bad kernel/stride");
-    MADM_REQUIRE(a->N > 0 && a->N % 4 == 0, "conv2d: N=%d must be a positive multiple of 4", a->N);
-    MADM_REQUIRE(a->epilogue >= MADM_EPI_NONE && a->epilogue <= MADM_EPI_RELU, "conv2d: bad epilogue");
-    MADM_REQUIRE(a->splitk >= 1, "conv2d: splitk must be >= 1");
-    const int ocols = (a->epilogue == MADM_EPI_GEGLU) ? a->N / 2 : a->N;
-    MADM_REQUIRE(a->ldo >= ocols && a->ldo % 2 == 0, "conv2d: ldo=%d too small/odd for %d columns", a->ldo, ocols);
-    MADM_REQUIRE(a->epilogue == MADM_EPI_GEGLU || a->ldo % 4 == 0, "conv2d: ldo must be a multiple of 4");
-    MADM_REQUIRE(!a->residual || (a->ldr >= ocols && a->ldr % 2 == 0), "conv2d: bad ldr");
-    p.in1 = (const char*)a->in1; p.in2 = (const char*)a->in2; p.w = (const char*)a->w;
-    p.bias = a->bias; p.rowvec = a->rowvec; p.residual = (const char*)a->residual;
-    p.out = (char*)a->out; p.ws = (float*)a->workspace; p.stats = a->stats;
-    p.gn_sums1 = nullptr; p.gn_sums2 = nullptr; p.gn_gamma = nullptr; p.gn_beta = nullptr;
-    p.gn_G = 0; p.gn_eps = 0.f; p.gn_magic = 0; p.act = 0;
-    p.ln_cs = a->ln_colsum; p.ln_eps = a->ln_eps;
-    if (a->ln_colsum) {
-        MADM_REQUIRE(a->KH == 1 && a->KW == 1 && a->stride == 1 && a->pad_t == 0 && a->pad_l == 0 && !a->upsample &&
-                     a->C2 == 0 && a->OH == a->IH && a->OW == a->IW,
-                     "conv2d: the folded LayerNorm needs a linear layer / 1x1 conv over ONE source (K = C1)");
-        MADM_REQUIRE(!a->gn_sums1 && a->ln_eps > 0.f && a->splitk == 1,
-                     "conv2d: folded LayerNorm: no fused GroupNorm, eps > 0, splitk == 1 (every block must see whole rows)");
-    }
-    MADM_REQUIRE(!a->stats || a->epilogue != MADM_EPI_GEGLU, "conv2d: fused statistics cannot follow GEGLU");
-    p.C1 = a->C1; p.C2 = a->C2; p.Ctot = a->C1 + a->C2;
-    p.B = a->B; p.IH = a->IH; p.IW = a->IW; p.OH = a->OH; p.OW = a->OW;
-    p.KH = a->KH; p.KW = a->KW; p.stride = a->stride; p.pad_t = a->pad_t; p.pad_l = a->pad_l;
-    p.upsample = a->upsample ? 1 : 0;
-    p.N = a->N; p.K = r.K; p.M = r.M;
-    MADM_REQUIRE(!a->rowvec || (a->ldrv >= a->N && a->ldrv % 4 == 0), "conv2d: bad ldrv=%d", a->ldrv);
-    p.ldr = a->ldr; p.ldo = a->ldo; p.ldrv = a->ldrv; p.epilogue = a->epilogue;
-    p.ldw = a->ldw ? a->ldw : p.K;
-    p.out_f32 = a->out_f32 ? 1 : 0;
-    MADM_REQUIRE(p.ldw >= p.K && p.ldw % (bke / 8) == 0, "conv2d: bad weight row stride ldw=%d", p.ldw);
-    MADM_REQUIRE(!p.out_f32 || (a->epilogue != MADM_EPI_GEGLU && !a->residual), "conv2d: out_f32 cannot follow GEGLU / residual");
-    p.ld1 = a->ld1 ? a->ld1 : a->C1;
-    p.ld2 = a->ld2 ? a->ld2 : a->C2;
-    MADM_REQUIRE(p.ld1 >= a->C1 && p.ld2 >= a->C2 && p.ld1 % (bke / 8) == 0 && p.ld2 % (bke / 8) == 0,
-                 "conv2d: bad source row strides ld1=%d ld2=%d", p.ld1, p.ld2);
-    {
-        const size_t es = madm_esize(a->dtype);
-        const size_t px = (size_t)a->B * a->IH * a->IW;
-        const size_t b1 = ((px - 1) * p.ld1 + a->C1) * es;
-        const size_t b2 = a->C2 ? ((px - 1) * p.ld2 + a->C2) * es : 0;
-        const size_t bw = ((size_t)(a->N - 1) * p.ldw + p.K) * es;
-        MADM_REQUIRE(b1 < 0x80000000ull && b2 < 0x80000000ull && bw < 0x80000000ull,
-                     "conv2d: tensors must stay below 2 GiB (32-bit buffer offsets)");
-        p.bytes1 = (unsigned)b1; p.bytes2 = (unsigned)b2; p.bytesw = (unsigned)bw;
-    }
-    p.nk = r.k_steps();
-    MADM_REQUIRE((long long)p.nk * (std::min(a->splitk, p.nk) + 1) < 0x7fffffffLL, "conv2d: K too large for the 32-bit slice arithmetic");
-    return MADM_OK;
-}
-
 template <typename T, int BM, int BN, int NS, bool LIN>
 int launch_glds_v(const IgemmP& p, dim3 grid, hipStream_t s) {
     constexpr size_t lds = (size_t)NS * (BM + BN) * 128;
@@ -1093,9 +751,24 @@ int launch_glds_v(const IgemmP& p, dim3 grid, hipStream_t s) {
     return madm_check_launch("igemm_glds_kernel");
 }
 
-template <typename T, int BM, int BN, int NS>
-int launch_glds(const IgemmP& p, dim3 grid, hipStream_t s, bool lin) {
-    return lin ? launch_glds_v<T, BM, BN, NS, true>(p, grid, s) : launch_glds_v<T, BM, BN, NS, false>(p, grid, s);
+// One row of MADM_CONV_TILES (conv_plan.hpp) -> its kernel instantiation.  LIN (the linear fast path): every GLDS tile, and the
+// register-staged tiles 2 and 3.
+template <typename T, int CODE, int BM, int BN, TileFamily F, int SLOTS>
+int launch_gemm_tile(const IgemmP& p, dim3 grid, hipStream_t s, bool lin) {
+    if constexpr (F == GLDS) {
+        return lin ? launch_glds_v<T, BM, BN, SLOTS, true>(p, grid, s) : launch_glds_v<T, BM, BN, SLOTS, false>(p, grid, s);
+    } else if constexpr (F == IGEMM) {
+        if constexpr (CODE == 2 || CODE == 3) {
+            if (lin) {
+                igemm_kernel<T, BM, BN, SLOTS, true><<<grid, 256, 0, s>>>(p);
+                return madm_check_launch("igemm_kernel");
+            }
+        }
+        igemm_kernel<T, BM, BN, SLOTS, false><<<grid, 256, 0, s>>>(p);
+        return madm_check_launch("igemm_kernel");
+    } else {
+        return MADM_ERR_UNSUPPORTED;   // the other families have launchers of their own (launch() below)
+    }
 }
 
 template <typename T>
@@ -1103,7 +776,7 @@ int launch(const IgemmP& p0, int t, hipStream_t s, const PostGn& pn) {
     IgemmP p = p0;
     const Tile& ti = *tile_info(t);
     const int bm = ti.bm, bn = ti.bn;
-    int rc;
+    int rc = MADM_ERR_UNSUPPORTED;
     if (ti.family == APANEL) return launch_igemm_apanel<T>(p, s);
     if (ti.family == H16) rc = launch_conv3x3_h16<T>(p, bn, s);
     else if (ti.family == HALO_DMA) rc = launch_conv3x3_halo_dma<T>(p, bn, s);
@@ -1114,20 +787,10 @@ int launch(const IgemmP& p0, int t, hipStream_t s, const PostGn& pn) {
         dim3 grid((unsigned)(tilesM * p.tilesN), 1, (unsigned)p.splitk);
         const bool lin = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && !p.upsample &&
                          p.OH == p.IH && p.OW == p.IW;
-        if (t == 1) igemm_kernel<T, 128, 128, 2, false><<<grid, 256, 0, s>>>(p);
-        else if (t == 2 && lin) igemm_kernel<T, 128, 64, 3, true><<<grid, 256, 0, s>>>(p);
-        else if (t == 2) igemm_kernel<T, 128, 64, 3, false><<<grid, 256, 0, s>>>(p);
-        else if (t == 6) igemm_kernel<T, 64, 64, 8, false><<<grid, 256, 0, s>>>(p);
-        else if (t == 7) { if (int e = launch_glds<T, 64, 64, 4>(p, grid, s, lin)) return e; }
-        else if (t == 8) { if (int e = launch_glds<T, 128, 64, 3>(p, grid, s, lin)) return e; }
-        else if (t == 11) { if (int e = launch_glds<T, 64, 64, 3>(p, grid, s, lin)) return e; }
-        else if (t == 14) { if (int e = launch_glds<T, 128, 128, 3>(p, grid, s, lin)) return e; }
-        else if (t == 15) { if (int e = launch_glds<T, 128, 128, 2>(p, grid, s, lin)) return e; }
-        else if (t == 16) { if (int e = launch_glds<T, 64, 64, 2>(p, grid, s, lin)) return e; }
-        else if (t == 17) { if (int e = launch_glds<T, 128, 64, 2>(p, grid, s, lin)) return e; }
-        else if (lin) igemm_kernel<T, 64, 64, 4, true><<<grid, 256, 0, s>>>(p);
-        else igemm_kernel<T, 64, 64, 4, false><<<grid, 256, 0, s>>>(p);
-        rc = madm_check_launch("igemm_kernel");
+#define MADM_TILE_LAUNCH(code, bm_, bn_, family, slots, name) \
+        if (t == code) rc = launch_gemm_tile<T, code, bm_, bn_, family, slots>(p, grid, s, lin);
+        MADM_CONV_TILES(MADM_TILE_LAUNCH)
+#undef MADM_TILE_LAUNCH
     }
     if (rc) return rc;
     if (p.splitk > 1 && pn.gamma) {
@@ -1167,42 +830,6 @@ int madm_debug_read_glds_stamps(unsigned long long* host, int n) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_glds_stamps), sizeof(unsigned long long) * n);
 }
 #endif
-
-void madm_debug_set_conv_tile(int t) { g_tile_override = t; }
-
-int madm_set_tuning_profile(int profile) {
-    MADM_REQUIRE(profile == 0 || profile == 1, "set_tuning_profile: 0 = throughput (side-by-side rows), 1 = latency (lone-launch rows)");
-    g_tuning_profile.store(profile, std::memory_order_relaxed);
-    return MADM_OK;
-}
-int madm_get_tuning_profile(void) { return g_tuning_profile.load(std::memory_order_relaxed); }
-
-const char* madm_conv2d_tile_name(int tile) { return tile_info(tile) ? tile_info(tile)->name : nullptr; }
-
-// A caller used to decide in stages, each on what the earlier ones had filled in (apanel_eligible looks at splitk and stats): split-K
-// suggested for the tile picked WITHOUT split-K and statistics, the post-GroupNorm asked with the split-K set and still no statistics,
-// the launch picked with everything set.  The same stages run here, on one copy of the request and one reading of the process state.
-int madm_conv2d_make_plan(const madm_conv2d_args* request, madm_conv2d_plan* plan) {
-    MADM_REQUIRE(request != nullptr && plan != nullptr, "conv2d plan: null argument");
-    MADM_REQUIRE(madm_dtype_ok(request->dtype), "conv2d plan: bad dtype %d", request->dtype);
-    MADM_REQUIRE(request->splitk >= 0, "conv2d plan: splitk must be 0 (the library chooses) or >= 1");
-    madm_conv2d_args c = *request;
-    const Request r(&c);
-    c.stats = nullptr; c.pn_gamma = nullptr;
-    if (request->splitk == 0) {
-        c.splitk = 1;
-        c.splitk = std::max(1, suggest_splitk(r));
-    }
-    resolve(r, *plan);
-    plan->post_gn = post_gn_fits(&c, plan->splitk_eff) ? 1 : 0;
-    if (!plan->post_gn && request->stats) {   // the statistics come from the conv's own epilogue
-        c.stats = request->stats;
-        resolve(r, *plan);
-    }
-    // a row was FOUND for the shape: the stride-2 -> plain fallback and the upsample lookup count
-    plan->tuned_row = ((h16_upsample_eligible(&c) && r.row(2)) || r.row(variant_of(&c))) ? 1 : 0;
-    return MADM_OK;
-}
 
 int madm_conv2d_fwd(const madm_conv2d_args* a, void* stream) {
     MADM_REQUIRE(a != nullptr, "conv2d: null args");
@@ -1248,6 +875,5 @@ int madm_conv2d_fwd(const madm_conv2d_args* a, void* stream) {
     return launch<bf16_t>(p, pl.tile, s, pn);
 }
 
-int madm_conv2d_can_fuse_groupnorm(const madm_conv2d_args* a) { return a && halo_eligible(a) ? 1 : 0; }
 
 }  // extern "C"

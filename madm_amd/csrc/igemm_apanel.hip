@@ -26,12 +26,6 @@
 
 namespace {
 
-#define AP_ASM(...) asm volatile(__VA_ARGS__)
-#if defined(__HIP_DEVICE_COMPILE__)
-template <int N> __device__ __forceinline__ void ap_wait_vmcnt() { AP_ASM("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void ap_wait_lgkmcnt() { AP_ASM("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-#endif
-
 #ifdef AP_STAMPS   // tools/exp/stamps_apanel.py: shader-clock timeline of wave 0 of workgroup 0
 __device__ unsigned long long g_ap_stamps[1024];
 #define AP_STAMP(k_) if (blockIdx.x == 0 && threadIdx.x == 0 && (k_) < 1024) g_ap_stamps[(k_)] = __builtin_readcyclecounter();
@@ -110,11 +104,7 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = (WM == 2) ? (wave >> 1) : 0, wn = (WM == 2) ? (wave & 1) : wave;
     const int KC = p.nk;                                  // 128-byte chunks per row
-    int bid = blockIdx.x;
-    {
-        const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = bid & 7, i = bid >> 3;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
+    const int bid = xcd_block_order();
     const int P = (p.M + BM - 1) / BM;
     const int chunk = bid / P, panel = bid - chunk * P;
     const int m0 = panel * BM;
@@ -182,7 +172,7 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
 
     // ---- every wave's panel pieces landed -> barrier; optional LayerNorm in place ----
     AP_STAMP(1);
-    AP_ASM("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     AP_STAMP(2);
     __builtin_amdgcn_s_barrier();
     AP_STAMP(3);
@@ -250,7 +240,7 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
                 }
             }
         }
-        AP_ASM("s_waitcnt lgkmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     }
 
@@ -284,10 +274,10 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
         else {
             const int ahead = (S - 1 - s < AP_NS - 2) ? S - 1 - s : AP_NS - 2;   // tiles requested after tile s
             const int young = ahead * WP;
-            if (young >= 8) ap_wait_vmcnt<8>();
-            else if (young == 4) ap_wait_vmcnt<4>();
-            else if (young == 2) ap_wait_vmcnt<2>();
-            else ap_wait_vmcnt<0>();
+            if (young >= 8) wait_vmcnt<8>();
+            else if (young == 4) wait_vmcnt<4>();
+            else if (young == 2) wait_vmcnt<2>();
+            else wait_vmcnt<0>();
         }
         AP_STAMP(8 + s * 4);
         AP_STAMP(8 + s * 4 + 1);
@@ -303,19 +293,19 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
                 const unsigned pa = aA[kk] + pofs, pb = aB[kk] + rofs;
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
-                    AP_ASM("ds_read_b128 %0, %1 offset:%2" : "=v"(af[kk][i]) : "v"(pa), "n"(i * 2048));
+                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(af[kk][i]) : "v"(pa), "n"(i * 2048));
 #pragma unroll
                 for (int j = 0; j < NI; ++j)
-                    AP_ASM("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[kk][j]) : "v"(pb), "n"(j * 2048));
+                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[kk][j]) : "v"(pb), "n"(j * 2048));
             }
-            ap_wait_lgkmcnt<MI + NI>();
+            wait_lgkmcnt<MI + NI>();
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < NI; ++j)
                     mma16<T>(__builtin_bit_cast(uint4, wf[0][j]), __builtin_bit_cast(uint4, af[0][i]), acc[i][j]);
-            ap_wait_lgkmcnt<0>();
+            wait_lgkmcnt<0>();
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < MI; ++i)
@@ -334,9 +324,9 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
                 const unsigned ba = bias_base + (unsigned)(nloc + 16 * j) * 4u;
-                AP_ASM("ds_read_b128 %0, %1" : "=v"(bv[j]) : "v"(ba));
+                asm volatile("ds_read_b128 %0, %1" : "=v"(bv[j]) : "v"(ba));
             }
-            ap_wait_lgkmcnt<0>();
+            wait_lgkmcnt<0>();
             const bool geglu = p.epilogue == MADM_EPI_GEGLU;
             // values first (the tiles requested for the next steps keep landing meanwhile), then the drain, then the stores
 #pragma unroll
@@ -352,7 +342,7 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
                     }
                     acc[i][j] = v;
                 }
-            ap_wait_vmcnt<0>();
+            wait_vmcnt<0>();
             landed = (S - 1 - s < AP_NS - 1) ? S - 1 - s : AP_NS - 1;
 #pragma unroll
             for (int i = 0; i < MI; ++i) {

@@ -1,5 +1,5 @@
-// Shared by igemm.hip (gather implicit GEMM) and conv3x3.hip (LDS halo-tile 3x3 conv): launch
-// parameters, the common epilogue and the split-K reduction interface.
+// Shared by the conv / GEMM kernels (igemm.hip, igemm_apanel.hip, conv3x3*.hip): launch parameters, the set-up helpers of
+// their prologues, the common epilogue and the split-K reduction interface.
 #pragma once
 #include "common.hpp"
 
@@ -20,6 +20,60 @@ struct IgemmP {
     // sums taken from the A fragments the waves read anyway (K = C: every block walks whole rows)
     const float* ln_cs; float ln_eps;
 };
+
+// ---- set-up helpers of the kernels' prologues --------------------------------------------------------------------------
+// XCD-aware order: blocks b and b+8 share an XCD (round-robin dispatch), so give every XCD a contiguous
+// range of tiles -- neighbouring output rows re-read the same input lines / weight panels from ITS L2.
+// (placement only changes speed; the remap is a bijection for any grid size)
+__device__ __forceinline__ int xcd_block_order() {
+    const int bid = blockIdx.x;
+    const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = bid & 7, i = bid >> 3;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
+}
+
+// Buffer descriptors rs1 / rs2 / rsw of the (one or two) sources and the weights, declared in the kernel: every global read is
+// a raw buffer load, so an out-of-range voffset (padding pixels, rows beyond M / N) returns zeros and the gathers are
+// branch-free.  No second source: a zero-sized descriptor on the first.
+#define IGEMM_OPERAND_DESCRIPTORS(p)                                                                                          \
+    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(p).in1, 0, (p).bytes1, 0x00020000);          \
+    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)((p).in2 ? (p).in2 : (p).in1), 0,             \
+                                                                         (p).in2 ? (p).bytes2 : 0u, 0x00020000);              \
+    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)(p).w, 0, (p).bytesw, 0x00020000)
+
+// slice z of `splitk`: steps [k0, k1) of the n K steps (igemm) / channel chunks (halo kernels)
+struct KSlice { int k0, k1; };
+__device__ __forceinline__ KSlice splitk_slice(int n, int z, int splitk) { return {(n * z) / splitk, (n * (z + 1)) / splitk}; }
+
+// igemm gather state of output row m < M: a_b = image row base (image * IH), (a_iy, a_ix) = input pixel of tap (0, 0).  LIN (see
+// igemm_glds_kernel): a_b = input row, a_iy >= 0 marks it valid (a row beyond M gets a_iy = -(1 << 24): never in range).
+// (Macro text like the two below it: as inline functions these changed the register allocation of the kernels around them.)
+#define IGEMM_ROW_DECODE(LIN, p, m, OHW, a_b, a_iy, a_ix)                                                   \
+    if constexpr (LIN) {                                                                                    \
+        a_b = (m); a_iy = 0; a_ix = 0;                                                                      \
+    } else {                                                                                                \
+        const int b = (m) / (OHW);                                                                          \
+        const int r = (m) - b * (OHW);                                                                      \
+        const int oy = r / (p).OW;                                                                          \
+        const int ox = r - oy * (p).OW;                                                                     \
+        a_b = b * (p).IH; a_iy = oy * (p).stride - (p).pad_t; a_ix = ox * (p).stride - (p).pad_l;           \
+    }
+
+// Declares c0, tr, ts = the tap state of the K tile that starts at element kbase (channel c0 of tap (tr, ts)), and IHe, IWe, ush =
+// the extent of the (upsampled) input.
+#define IGEMM_TAP_STATE(LIN, p, kbase_)                                                                     \
+    int c0, tr, ts;                                                                                         \
+    if constexpr (LIN) {                                                                                    \
+        c0 = (kbase_); tr = 0; ts = 0;      /* one tap: k = channel */                                      \
+    } else {                                                                                                \
+        const int kbase = (kbase_);                                                                         \
+        const int tap = kbase / (p).Ctot;                                                                   \
+        c0 = kbase - tap * (p).Ctot;                                                                        \
+        tr = tap / (p).KW;                                                                                  \
+        ts = tap - tr * (p).KW;                                                                             \
+    }                                                                                                       \
+    const int IHe = (p).upsample ? 2 * (p).IH : (p).IH;                                                     \
+    const int IWe = (p).upsample ? 2 * (p).IW : (p).IW;                                                     \
+    const int ush = (p).upsample ? 1 : 0
 
 // Row sums of one 16-byte A-fragment chunk (the lane's row, 8 / 4 consecutive k): s += sum x, q += sum x^2 (f32).
 template <typename T> __device__ __forceinline__ void ln_accum(const uint4& a, float& s, float& q);

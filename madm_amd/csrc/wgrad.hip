@@ -37,7 +37,6 @@ __global__ __launch_bounds__(256, 2) void conv2d_wgrad_kernel(const WgradP p) {
     constexpr int LI = PX / RPP;                 // passes (2)
     constexpr int ROWB = 128 * (int)sizeof(T) + (sizeof(T) == 2 ? 32 : 16);   // padded: transposed reads conflict-free
     constexpr int TILEB = PX * ROWB;
-    constexpr unsigned OOB = 0x80000000u;
     __shared__ __attribute__((aligned(16))) char smem[4 * TILEB];   // {dout, A} x 2 stages
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

@@ -33,7 +33,8 @@ def kernels(path):
             ln = ln.strip().lstrip("- ").strip()
             if ln.startswith(".name:"):
                 cur["name"] = ln.split(":", 1)[1].strip()
-            for k in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count"):
+            for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count", "agpr_count", "sgpr_count",
+                      "vgpr_spill_count", "sgpr_spill_count"):
                 if ln.startswith("." + k + ":"):
                     cur[k] = int(ln.split(":")[1])
             if ln.startswith(".wavefront_size:") and "name" in cur:
