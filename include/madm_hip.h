@@ -640,6 +640,24 @@ typedef struct {
 int madm_vis_compose(const madm_vis_tile* tiles, int n, int B, int H, int W, int cols_max,
                      const unsigned char* palette768, unsigned char* canvas, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * The evaluator's per-image export (evaluation/d2_evaluator.py:156-183 save_vis_results with eval_only): ONE launch writes
+ * the pixel data of the four PNG files of an image, already as PNG scanlines (each row: filter byte 0, then the samples),
+ * into one contiguous buffer of H * (4 + 11 W) bytes.  Planes, in this order:
+ *   image       H rows of 1 + 3W bytes  np.uint8(image): f32 values truncated toward zero (saturated to [0, 255], NaN ->
+ *                                       0), u8 values copied; image is [3][H][W]
+ *   pred        H rows of 1 + 2W bytes  the class id as a 16-bit BIG-endian sample (PNG bit depth 16, colour type 0: what
+ *                                       PIL writes for an int32 array)
+ *   pred_color  H rows of 1 + 3W bytes  palette768[3 * (pred & 255) + c]
+ *   gt_color    H rows of 1 + 3W bytes  palette768[3 * (gt' & 255) + c], gt' = num_classes where gt == ignore_label
+ *                                       (d2_evaluator.py:122; the zero-padded palette makes those pixels black)
+ * pred, gt: i64 [H * W].  ``out`` needs no alignment; EVERY byte of it is written.  H * (4 + 11 W) < 2^31.
+ * ------------------------------------------------------------------------------- */
+typedef enum { MADM_EXPORT_IMAGE_F32 = 0, MADM_EXPORT_IMAGE_U8 = 1 } madm_export_image_kind;
+int madm_eval_export_pack(const void* pred, const void* gt, const void* image, int image_kind,
+                          const unsigned char* palette768, int num_classes, int ignore_label, int H, int W,
+                          unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

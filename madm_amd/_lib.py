@@ -105,6 +105,7 @@ class AttentionBwdArgs(ctypes.Structure):
 
 VIS_IMAGE, VIS_LABEL, VIS_LOGITS, VIS_HEAT = 0, 1, 2, 3
 VIS_MAX_TILES = 16
+EXPORT_IMAGE_F32, EXPORT_IMAGE_U8 = 0, 1
 
 
 class VisTile(ctypes.Structure):
@@ -222,6 +223,8 @@ SYMBOLS = [
     ("madm_causal_attention_fwd", c_int, [ctypes.POINTER(AttentionArgs), c_void_p]),
     ("madm_quick_gelu", c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     ("madm_vis_compose", c_int, [ctypes.POINTER(VisTile), c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("madm_eval_export_pack", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                      c_void_p]),
 ]
 
 

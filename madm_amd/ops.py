@@ -1044,6 +1044,34 @@ def vis_compose(tiles, B, H, W, cols_max, palette, canvas):
     return canvas
 
 
+def eval_export_pack_bytes(H, W):
+    """Size of the pack buffer of one H x W image: three RGB8 planes of H * (1 + 3W) and one 16-bit plane of H * (1 + 2W)."""
+    return int(H) * (4 + 11 * int(W))
+
+
+def eval_export_pack(pred, gt, image, palette, num_classes, ignore_label, out=None):
+    """One launch: the PNG scanlines (filter byte 0 + samples per row) of the evaluator's four per-image files -- image,
+    pred (16-bit big-endian), pred_color, gt_color, in this order (layout in include/madm_hip.h) -- into ``out`` u8
+    [H * (4 + 11 W)].  pred, gt: i64 [H, W]; image: f32 or u8 [3, H, W]; ``palette`` u8 [768] on the device.  ``out`` may
+    start at any byte offset; every byte of it is written."""
+    _need_cuda(pred, gt, image, palette, out)
+    assert pred.dtype == torch.int64 and gt.dtype == torch.int64 and pred.is_contiguous() and gt.is_contiguous()
+    assert pred.dim() == 2 and gt.shape == pred.shape, f"pred {tuple(pred.shape)} gt {tuple(gt.shape)}"
+    H, W = pred.shape
+    assert image.dtype in (torch.float32, torch.uint8) and image.is_contiguous() and tuple(image.shape) == (3, H, W), \
+        f"image {image.dtype} {tuple(image.shape)}"
+    assert palette.dtype == torch.uint8 and palette.numel() == 768 and palette.is_contiguous()
+    n = eval_export_pack_bytes(H, W)
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint8, device=pred.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n, "pack buffer size does not match H, W"
+    kind = _lib.EXPORT_IMAGE_U8 if image.dtype == torch.uint8 else _lib.EXPORT_IMAGE_F32
+    check(lib.madm_eval_export_pack(pred.data_ptr(), gt.data_ptr(), image.data_ptr(), kind, palette.data_ptr(),
+                                    int(num_classes), int(ignore_label), H, W, out.data_ptr(), _stream()),
+          "madm_eval_export_pack")
+    return out
+
+
 def scale_pad_nchw(x, scale, OH, OW, y1=0, x1=0, out=None):
     """x[:, :, y1:y1+OH, x1:x1+OW] * scale with zeros outside x (f32 NCHW): padding, cropping, window extraction."""
     _need_cuda(x, out)
