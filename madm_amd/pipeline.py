@@ -1,6 +1,6 @@
 """Throughput launch strategy for LdmRocm.forward / MadmInference.forward: hipGraph executables on several HIP streams,
 fed with a NEW batch per submit the way the reference's inference loop feeds its model
-(/root/reference/evaluation/evaluator.py:75-93: ``for idx, inputs in enumerate(data_loader): outputs = model(inputs)``).
+(the reference's evaluation/evaluator.py:75-93: ``for idx, inputs in enumerate(data_loader): outputs = model(inputs)``).
 
 ``StagedExtractor`` -- the two stages of the extractor as separate graphs on separate streams.
 Stage 1 (``LdmRocm._stage_encode``: normalise -> vae_encoder -> timestep draw -> add_noise, ldm_diffusers.py:143-163) is
@@ -16,13 +16,24 @@ by side and the next encoder slides under them.  Each in-flight batch owns a SLO
 DAFormer head -> resize) as one graph per slot, slots round-robin on ``streams`` streams (default 4: one per hardware pipe of
 the queue scheduler; a fifth stream shares a pipe and loses 15 %), same submit contract.
 
+``StagedInference`` -- the same forward as three graphs per slot (VAE encoder | UNet | VAE decoder + projections + head), the
+whole-model analogue of ``StagedExtractor``: encoder and decoder stages on a stream each, the UNet stages of consecutive
+images side by side on ``unet_streams`` streams.
+
+All three are a ``_SlotRunner``: a ring of slots, each a list of (stream, graph) stages replayed in order and linked by events;
+the classes differ in how the streams are made, how a slot is captured and how the caller's inputs are checked and copied in.
+
 The reference's per-call input-range assert (ldm_diffusers.py:147: ``assert -1 <= images.min() and images.max() <= 1``, a host
 sync per call) is kept as a DEFERRED check: the stem kernel's min / max probe of every submitted batch is copied to a pinned
 ring behind the encoder and compared on the host as soon as a later ``submit`` / ``drain`` finds it completed -- the
 ``AssertionError`` comes a few submits late instead of stalling the device once per batch.
 
-Same kernels, same per-batch results as ``LdmRocm.forward`` (tests/test_parity_gpu.py::test_staged_pipeline_*: distinct batches
-per submit, every slot bit-identical to ``forward()`` on ITS batch); only the order in which the GPU sees the launches changes.
+Same kernels as the synchronous ``forward()``; only the order in which the GPU sees the launches changes.  The graphs are
+captured under the THROUGHPUT rows of the tile table (``ops.tuning_profile("throughput", pin=True)``), a synchronous call
+takes the lone-launch rows of the latency profile by default (other tiles / split-K: another summation order), so every slot
+is bit-identical to ``forward()`` on ITS batch when that call runs under the same tuning profile -- inside
+``ops.tuning_profile("throughput", pin=True)`` or with ``MADM_SYNC_PROFILE=throughput`` -- and equal to rounding noise
+otherwise (tests/test_parity_gpu.py::test_staged_pipeline_*, tests/test_eval_gpu.py: distinct batches per submit).
 """
 import os
 import warnings
@@ -125,13 +136,131 @@ def _queues_warning(n, who):
                       f"serialise; export GPU_MAX_HW_QUEUES>={n} before the process starts")
 
 
-class StagedExtractor:
+def _warm_and_capture(stream, cur, fn):
+    """``fn()`` once eagerly on ``stream`` (behind ``cur``: sizes the stream's workspaces outside the capture), then captured:
+    returns (graph, what the captured call returned)."""
+    stream.wait_stream(cur)
+    with torch.cuda.stream(stream):
+        fn()
+    stream.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=stream):
+        out = fn()
+    return g, out
+
+
+class _SlotRunner:
+    """What the three runners share.  A subclass creates its streams and captures, per slot, a list of stages
+    ``[(stream, graph), ...]``, hands them to ``_arm`` and supplies the hooks at the end of this class; ``submit`` then runs
+    one protocol for all of them.  The ORDER of what a submit enqueues is performance-relevant and pinned
+    by tests/test_pipeline_order_gpu.py."""
+
+    def _arm(self, ldm, streams, stages, probes, range_check):
+        """Construction tail, after the captures.  ``probes[j]``: the stem's (min, max) tensor of slot j, or None."""
+        torch.cuda.synchronize(self.device)
+        self._streams = list(streams)
+        self.stages = stages
+        self._probes = probes
+        # a slot's buffers are free again when its LAST stage has finished; the first stage has to wait for that unless both
+        # run on one stream (stream order does it)
+        self._wait_done = [st[-1][0] != st[0][0] for st in stages]
+        self._links = [[torch.cuda.Event() for _ in st[1:]] for st in stages]       # stage i -> stage i + 1
+        self.done = [torch.cuda.Event() for _ in range(self.n_slots)]
+        self._ready = [torch.cuda.Event() for _ in range(2 * self.n_slots)]           # submits in flight never share one
+        self.turn = 0
+        if range_check is None:
+            range_check = bool(ldm.check_input_range)
+        self.range_check = DeferredRangeCheck(self.device) if (range_check and probes[0] is not None) else None
+
+    @property
+    def streams(self):
+        return list(self._streams)
+
+    def submit(self, batched_inputs):
+        """Enqueues one batch on the next slot and returns ``Submitted``: the slot's output tensors are valid once its ``done``
+        event has fired and stay so until the slot comes round again (``n_slots`` submits later) -- consume them on the host
+        after ``done.synchronize()`` or on a stream after ``stream.wait_event(done)``; a consumer that works on ANOTHER stream
+        than the slot's last stage must have finished (or be waited for) before that later submit.
+
+        The caller's tensors are read by copies enqueued on the slot's FIRST stream, behind an event recorded on the caller's
+        current stream (``sync_inputs``: whatever produced them there is finished first).  Like the source of any asynchronous
+        copy they must not be overwritten before the copies ran: ``.taken`` of the result fires then (dropping them is safe).
+        Raises the deferred range ``AssertionError`` of an EARLIER batch when its probe has arrived."""
+        self._check_inputs(batched_inputs)
+        if self.range_check is not None:
+            self.range_check.make_room()       # may raise an EARLIER batch's assert -- before anything of this submit is enqueued
+        turn = self.turn
+        j = turn % self.n_slots
+        self.turn += 1
+        (s0, g0), later = self.stages[j][0], self.stages[j][1:]
+        events = [*self._links[j], self.done[j]]
+        ready = None
+        if self._behind_caller(batched_inputs):
+            ready = self._ready[turn % len(self._ready)]
+            ready.record(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s0):
+            if ready is not None:
+                s0.wait_event(ready)
+            if turn >= self.n_slots and self._wait_done[j]:
+                s0.wait_event(self.done[j])                    # the slot's input and hand-over buffers are free again
+            self._copy_inputs(j, batched_inputs, s0)
+            taken = torch.cuda.Event()         # one per submit: the caller may hold it for as long as it likes
+            taken.record(s0)
+            g0.replay()
+            if later:
+                events[0].record(s0)
+            if self.range_check is not None:
+                self.range_check.push(self._probes[j], s0, turn)
+            if not later:
+                events[0].record(s0)           # a one-stage slot: ``done`` is behind the probe's copy too
+        for i, (s, g) in enumerate(later):
+            with torch.cuda.stream(s):
+                s.wait_event(events[i])
+                g.replay()
+                events[i + 1].record(s)
+        return Submitted(self._result(j), taken, turn)
+
+    def _synchronize(self):
+        for s in self._streams:
+            s.synchronize()
+
+    def drain(self):
+        """Waits for everything submitted and runs the range checks still pending."""
+        self._synchronize()
+        if self.range_check is not None:
+            self.range_check.drain()
+
+    def quiesce(self):
+        """Waits for the streams and DROPS the pending range checks (error paths: leave nothing in flight, raise nothing)."""
+        self._synchronize()
+        if self.range_check is not None:
+            self.range_check.discard()
+
+    def fork(self, stream=None):
+        """The pipeline's streams start after everything queued on ``stream`` (default: the current one)."""
+        stream = stream or torch.cuda.current_stream()
+        for s in self._streams:
+            s.wait_stream(stream)
+
+    def join(self, stream=None):
+        stream = stream or torch.cuda.current_stream()
+        for s in self._streams:
+            stream.wait_stream(s)
+
+    # A subclass supplies: _check_inputs(batched_inputs) -- refuses (AssertionError) what the graphs were not captured for, before
+    # anything is enqueued; _behind_caller(batched_inputs) -- whether the input copies are ordered behind the caller's current
+    # stream (an event record there + a wait); _copy_inputs(j, batched_inputs, stream) -- copies the caller's tensors into slot j's
+    # static buffers, with ``stream`` (the first stage's) current; _result(j) -- the tuple ``submit`` hands back.
+
+
+class StagedExtractor(_SlotRunner):
     """``pipe = StagedExtractor(ldm, example_inputs); outs, done = pipe.submit(batched_inputs)``.
 
     ``example_inputs`` fixes what the graphs are captured for: tensor shapes, the presence of ``cond_emb`` and the
     ``timestep`` range (a construction-time constant, like every other non-tensor entry).  ``submit`` takes a dict with the
     same keys as ``LdmRocm.forward`` (``img`` [B,3,H,W] f32, ``cond_inputs`` [B,77,768], ``cond_emb`` [B,1,1280] | None) on the
-    pipeline's device, or in host memory (pinned for an asynchronous transfer: copied in on the encoder stream)."""
+    pipeline's device, or in host memory (pinned for an asynchronous transfer: copied in on the encoder stream), and returns
+    ``Submitted`` = (outputs, done event)."""
 
     def __init__(self, ldm, example_inputs, unet_streams=3, streams=None, sync_inputs=True, range_check=None, slots=None,
                  **kwargs):
@@ -188,108 +317,47 @@ class StagedExtractor:
             assert d['img'].dtype == torch.float32, "img is handed over as f32 NCHW (the stem kernel normalises it)"
             d.update(self.const_inputs)
             self.static.append(d)
-        self.enc_graphs, self.unet_graphs, self.slots, self.outs = [], [], [], []
+        self.slots, self.outs = [], []         # per slot: the encoder's hand-over, the output tensors
+        enc_graphs, stages = [], []
         cur = torch.cuda.current_stream(dev)
+
+        def unet_stage(j):
+            ops.ARENA.reset(dev)               # the statistics arena of this stage: zeroed inside the graph
+            return ldm._stage_unet(self.slots[j], self.static[j], **kwargs)
+
         # the graphs hold the THROUGHPUT rows of the tile table (launches of several batches side by side): pinned, so that nothing
         # inside switches to the lone-launch profile of a synchronous forward (ops.tuning_profile)
         with torch.no_grad(), ops.tuning_profile("throughput", pin=True):
             for j in range(self.n_slots):
-                self.s_enc.wait_stream(cur)
-                with torch.cuda.stream(self.s_enc):
-                    ldm._stage_encode(self.static[j])          # sizes this stream's workspaces outside the capture
-                self.s_enc.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=self.s_enc):
-                    st = ldm._stage_encode(self.static[j])
-                self.enc_graphs.append(g)
+                g, st = _warm_and_capture(self.s_enc, cur, lambda: ldm._stage_encode(self.static[j]))
+                enc_graphs.append(g)
                 self.slots.append(st)
             for j in range(self.n_slots):
                 s = self.s_unet[j % self.k]
-                s.wait_stream(cur)
-                with torch.cuda.stream(s):
-                    ops.ARENA.reset(dev)
-                    ldm._stage_unet(self.slots[j], self.static[j], **kwargs)
-                s.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=s):
-                    ops.ARENA.reset(dev)                       # the statistics arena of this stage: zeroed inside the graph
-                    self.outs.append(ldm._stage_unet(self.slots[j], self.static[j], **kwargs))
-                self.unet_graphs.append(g)
-        torch.cuda.synchronize(dev)
-        self.encoded = [torch.cuda.Event() for _ in range(self.n_slots)]
-        self.done = [torch.cuda.Event() for _ in range(self.n_slots)]
-        self._ready = [torch.cuda.Event() for _ in range(2 * self.n_slots)]
-        self.turn = 0
-        if range_check is None:
-            range_check = bool(ldm.check_input_range)
-        has_probe = self.slots[0].get("minmax") is not None
-        self.range_check = DeferredRangeCheck(dev) if (range_check and has_probe) else None
+                g, out = _warm_and_capture(s, cur, lambda: unet_stage(j))
+                self.outs.append(out)
+                stages.append([(self.s_enc, enc_graphs[j]), (s, g)])
+        self._arm(ldm, [self.s_enc, *self.s_unet], stages, [st.get("minmax") for st in self.slots], range_check)
 
-    @property
-    def streams(self):
-        return [self.s_enc, *self.s_unet]
-
-    def submit(self, batched_inputs):
-        """Enqueues one batch; returns ``Submitted`` = (outputs, event): the slot's output tensors are valid once ``event`` has
-        fired and stay so until the slot comes round again (``slots`` submits later; default = ``unet_streams``) -- consume them on the host after
-        ``event.synchronize()`` or on a stream after ``stream.wait_event(event)``; a consumer that works on ANOTHER stream
-        than the slot's UNet stream must have finished (or be waited for) before that later submit.
-
-        The caller's tensors are read by copies enqueued on the ENCODER stream, behind an event recorded on the caller's
-        current stream (``sync_inputs``: whatever produced them there is finished first).  Like the source of any asynchronous
-        copy they must not be overwritten before the copies ran: ``.taken`` of the result fires then (dropping them is safe).
-        Raises the deferred range ``AssertionError`` of an EARLIER batch when its probe has arrived."""
+    def _check_inputs(self, batched_inputs):
         for k_ in {*self.const_inputs, *batched_inputs} - set(self.tensor_keys):
             v, got = self.const_inputs.get(k_), batched_inputs.get(k_)
             assert not torch.is_tensor(got) and got == v, \
                 f"StagedExtractor: '{k_}' = {v!r} is fixed at construction (captured in the graphs), got {got!r}"
-        if self.range_check is not None:
-            self.range_check.make_room()       # may raise an EARLIER batch's assert -- before anything of this submit is enqueued
-        j = self.turn % self.n_slots
-        first = self.turn < self.n_slots
-        turn = self.turn
-        self.turn += 1
-        st = self.static[j]
-        if self.sync_inputs:
-            ready = self._ready[turn % len(self._ready)]
-            ready.record(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self.s_enc):
-            if self.sync_inputs:
-                self.s_enc.wait_event(ready)
-            if not first:
-                self.s_enc.wait_event(self.done[j])            # the slot's input and hand-over buffers are free again
-            # host tensors (pinned: asynchronous) are transferred here too, in stream order in front of their encoder: measured
-            # against a transfer stream of the pipeline's own with a staging ring, 2 x 3 x 512 x 512 f32 per step from pinned
-            # memory, same box: 358.5 images/s from HBM, 323 .. 333 this way, 307 with the transfer stream (a fifth stream shares
-            # a hardware pipe with one of the four working ones, DESIGN.md section 6)
-            for k_ in self.tensor_keys:
-                _copy_checked(st[k_], batched_inputs.get(k_), k_, self.s_enc)
-            taken = torch.cuda.Event()         # one per submit: the caller may hold it for as long as it likes
-            taken.record(self.s_enc)
-            self.enc_graphs[j].replay()
-            self.encoded[j].record(self.s_enc)
-            if self.range_check is not None:
-                self.range_check.push(self.slots[j]["minmax"], self.s_enc, turn)
-        s = self.s_unet[j % self.k]
-        with torch.cuda.stream(s):
-            s.wait_event(self.encoded[j])
-            self.unet_graphs[j].replay()
-            self.done[j].record(s)
-        return Submitted((self.outs[j], self.done[j]), taken, turn)
 
-    def drain(self):
-        """Waits for everything submitted and runs the range checks still pending."""
-        for s in self.streams:
-            s.synchronize()
-        if self.range_check is not None:
-            self.range_check.drain()
+    def _behind_caller(self, batched_inputs):
+        return self.sync_inputs               # host tensors too: the caller may have filled a pinned buffer from its stream
 
-    def quiesce(self):
-        """Waits for the streams and DROPS the pending range checks (error paths: leave nothing in flight, raise nothing)."""
-        for s in self.streams:
-            s.synchronize()
-        if self.range_check is not None:
-            self.range_check.discard()
+    def _copy_inputs(self, j, batched_inputs, stream):
+        # host tensors (pinned: asynchronous) are transferred here too, in stream order in front of their encoder: measured
+        # against a transfer stream of the pipeline's own with a staging ring, 2 x 3 x 512 x 512 f32 per step from pinned
+        # memory, same box: 358.5 images/s from HBM, 323 .. 333 this way, 307 with the transfer stream (a fifth stream shares
+        # a hardware pipe with one of the four working ones)
+        for k_ in self.tensor_keys:
+            _copy_checked(self.static[j][k_], batched_inputs.get(k_), k_, stream)
+
+    def _result(self, j):
+        return self.outs[j], self.done[j]
 
     def concurrency_probe(self, reps=3):
         """Detects streams that share a hardware pipe: time of the k UNet graphs side by side on their k streams over k
@@ -303,8 +371,9 @@ class StagedExtractor:
             t0 = time.perf_counter()
             for _ in range(reps):
                 for j in js:
-                    with torch.cuda.stream(self.s_unet[j]):
-                        self.unet_graphs[j].replay()
+                    s, g = self.stages[j][1]   # slot j < k: its UNet graph, on s_unet[j]
+                    with torch.cuda.stream(s):
+                        g.replay()
             torch.cuda.synchronize(dev)
             return (time.perf_counter() - t0) / reps
 
@@ -313,169 +382,116 @@ class StagedExtractor:
         side = timed(range(self.k))
         return side / (self.k * one)
 
-    def fork(self, stream=None):
-        """The pipeline's streams start after everything queued on ``stream`` (default: the current one)."""
-        stream = stream or torch.cuda.current_stream()
-        for s in self.streams:
-            s.wait_stream(stream)
 
-    def join(self, stream=None):
-        stream = stream or torch.cuda.current_stream()
-        for s in self.streams:
-            stream.wait_stream(s)
+class _ImageRunner(_SlotRunner):
+    """The two runners of ``MadmInference.forward``: ``submit(batched_inputs)`` takes the reference's
+    ``[{'target_second_modality': [3,H,W]}]`` list (0 .. 255 values, any float / uint8 dtype, host or device), copies the image
+    into the slot's static f32 buffer and returns ``Submitted`` = (``[{'sem_seg': [1,K,H,W]}]``, done event, slot).  One image
+    size per runner (the graphs are captured for it); the extractor's range assert is deferred as in ``StagedExtractor``.  Work
+    enqueued on ``stream_of(slot)`` after a submit is ordered behind the slot's outputs and in front of its next round."""
+    streams_ = _SlotRunner.streams      # the name these two runners had for it
+
+    def _begin(self, model, example_inputs, n_streams):
+        _queues_warning(n_streams, type(self).__name__)
+        assert len(example_inputs) == 1
+        self.model = model
+        self.device = next(model.parameters()).device
+        self.ldm = model.backbone.feature_extractor.ldm_extractor
+        self.static, self.outs = [], []
+        return example_inputs[0]['target_second_modality']
+
+    def _static_call(self, ex):
+        x = torch.empty(tuple(ex.shape), dtype=torch.float32, device=self.device).copy_(ex)
+        self.static.append(x)
+        return [{'target_second_modality': x}]
+
+    def _check_inputs(self, batched_inputs):
+        assert len(batched_inputs) == 1 and 'modality_type' not in batched_inputs[0]
+        shape, want = tuple(batched_inputs[0]['target_second_modality'].shape), tuple(self.static[0].shape)
+        assert shape == want, f"{type(self).__name__}: captured for images of shape {want}, got {shape}"
+
+    def _behind_caller(self, batched_inputs):
+        return self.sync_inputs and batched_inputs[0]['target_second_modality'].is_cuda
+
+    def _copy_inputs(self, j, batched_inputs, stream):
+        x = batched_inputs[0]['target_second_modality']
+        self.static[j].copy_(x, non_blocking=True)          # dtype conversion (uint8 -> f32) included
+        if x.is_cuda:
+            x.record_stream(stream)
+
+    def _result(self, j):
+        return self.outs[j], self.done[j], j
 
 
-class GraphedInference:
+class GraphedInference(_ImageRunner):
     """``MadmInference.forward`` (mtmadise.py:657-691) as one hipGraph per slot; slots round-robin on ``streams`` streams, so
-    ``streams`` images are in flight.  ``submit(batched_inputs)`` takes the reference's ``[{'target_second_modality': [3,H,W]}]``
-    list (0 .. 255 values, any float / uint8 dtype, host or device), copies the image into the slot's static buffer and
-    returns (``[{'sem_seg': [1,K,H,W]}]``, event).  One image size per runner (the graphs are captured for it); the
-    extractor's range assert is deferred as in ``StagedExtractor``."""
+    ``streams`` images are in flight.  ``submit``: see ``_ImageRunner``."""
 
     def __init__(self, model, example_inputs, streams=4, slots=None, sync_inputs=True, range_check=None):
-        self.model = model
         self.n_streams = int(streams)
         self.n_slots = int(slots or streams)
         assert self.n_slots >= self.n_streams >= 1
         self.sync_inputs = bool(sync_inputs)
-        _queues_warning(self.n_streams, "GraphedInference")
-        assert len(example_inputs) == 1
-        dev = next(model.parameters()).device
-        self.device = dev
-        ex = example_inputs[0]['target_second_modality']
-        ldm = model.backbone.feature_extractor.ldm_extractor
-        self.ldm = ldm
-        self.streams_ = [torch.cuda.Stream(device=dev) for _ in range(self.n_streams)]
-        self.static, self.graphs, self.outs, self.minmax = [], [], [], []
-        cur = torch.cuda.current_stream(dev)
+        ex = self._begin(model, example_inputs, self.n_streams)
+        ss = [torch.cuda.Stream(device=self.device) for _ in range(self.n_streams)]
+        stages, probes = [], []
+        cur = torch.cuda.current_stream(self.device)
         with torch.no_grad(), ops.tuning_profile("throughput", pin=True):
             for j in range(self.n_slots):
-                s = self.streams_[j % self.n_streams]
-                x = torch.empty(tuple(ex.shape), dtype=torch.float32, device=dev).copy_(ex)
-                call = [{'target_second_modality': x}]
-                s.wait_stream(cur)
-                with torch.cuda.stream(s):
-                    model(call)                     # sizes this stream's workspaces outside the capture
-                s.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=s):
-                    out = model(call)
-                self.static.append(x)
-                self.graphs.append(g)
+                call = self._static_call(ex)
+                s = ss[j % self.n_streams]
+                g, out = _warm_and_capture(s, cur, lambda: model(call))
+                stages.append([(s, g)])
                 self.outs.append(out)
-                self.minmax.append(getattr(ldm, "last_minmax", None))
-        torch.cuda.synchronize(dev)
-        self.done = [torch.cuda.Event() for _ in range(self.n_slots)]
-        self._ready = [torch.cuda.Event() for _ in range(2 * self.n_slots)]
-        self.turn = 0
-        if range_check is None:
-            range_check = bool(ldm.check_input_range)
-        self.range_check = DeferredRangeCheck(dev) if (range_check and self.minmax[0] is not None) else None
+                probes.append(getattr(self.ldm, "last_minmax", None))
+        self._arm(self.ldm, ss, stages, probes, range_check)
 
     def stream_of(self, slot):
-        return self.streams_[slot % self.n_streams]
-
-    def submit(self, batched_inputs):
-        """Returns ``Submitted`` = (outputs, event, slot).  The outputs stay valid until the slot comes round again (``slots``
-        submits later); work enqueued on ``stream_of(slot)`` before that is ordered in front of the slot's next replay by
-        itself.  A device image must not be overwritten before ``.taken`` of the result has fired (see ``Submitted``)."""
-        assert len(batched_inputs) == 1 and 'modality_type' not in batched_inputs[0]
-        if self.range_check is not None:
-            self.range_check.make_room()
-        j = self.turn % self.n_slots
-        turn = self.turn
-        self.turn += 1
-        s = self.stream_of(j)
-        x = batched_inputs[0]['target_second_modality']
-        assert tuple(x.shape) == tuple(self.static[j].shape), \
-            f"GraphedInference: captured for images of shape {tuple(self.static[j].shape)}, got {tuple(x.shape)}"
-        if self.sync_inputs and x.is_cuda:
-            ready = self._ready[turn % len(self._ready)]
-            ready.record(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            if self.sync_inputs and x.is_cuda:
-                s.wait_event(ready)
-            self.static[j].copy_(x, non_blocking=True)          # dtype conversion (uint8 -> f32) included
-            if x.is_cuda:
-                x.record_stream(s)
-            taken = torch.cuda.Event()
-            taken.record(s)
-            self.graphs[j].replay()
-            if self.range_check is not None:
-                self.range_check.push(self.minmax[j], s, turn)
-            self.done[j].record(s)
-        return Submitted((self.outs[j], self.done[j], j), taken, turn)
-
-    def drain(self):
-        for s in self.streams_:
-            s.synchronize()
-        if self.range_check is not None:
-            self.range_check.drain()
-
-    def quiesce(self):
-        """Waits for the streams and DROPS the pending range checks (error paths: leave nothing in flight, raise nothing)."""
-        for s in self.streams_:
-            s.synchronize()
-        if self.range_check is not None:
-            self.range_check.discard()
+        return self._streams[slot % self.n_streams]
 
 
-class StagedInference:
+class StagedInference(_ImageRunner):
     """``MadmInference.forward`` (mtmadise.py:657-691) as THREE hipGraphs per slot -- VAE encoder | UNet | VAE decoder +
     projections + head -- the whole-model analogue of ``StagedExtractor``.  The two chip-filling stages run on
     streams of their own (encoder: high priority, the pipeline's pacemaker; decoder + head), the small-grid UNet stages of
     consecutive images side by side on ``unet_streams`` streams: four streams = the four hardware pipes of the queue scheduler.
     The stage boundaries are ``LdmRocm.stage_hook`` calls inside ONE ordinary ``model(batched_inputs)`` call: during capture the
     hook ends the running stream capture and begins the next one on the next stage's stream, so every module between the
-    boundaries is captured exactly as the eager forward runs it (same kernels, same values: the slot outputs are bit-identical
-    to ``model(batched_inputs)``).  ``submit`` has ``GraphedInference``'s contract."""
+    boundaries is captured exactly as the eager forward runs it: same kernels, and the slot outputs are bit-identical to
+    ``model(batched_inputs)`` under the tuning profile of the capture (``ops.tuning_profile("throughput", pin=True)`` around the
+    call, or ``MADM_SYNC_PROFILE=throughput``; a plain synchronous call takes the latency profile's rows and agrees to rounding
+    noise).  ``submit``: see ``_ImageRunner``."""
 
     def __init__(self, model, example_inputs, unet_streams=2, slots=None, sync_inputs=True, range_check=None):
-        self.model = model
         self.k = int(unet_streams)
         self.n_slots = int(slots or 2 * (self.k + 1))
         assert self.k >= 1 and self.n_slots >= self.k
         self.sync_inputs = bool(sync_inputs)
-        _queues_warning(self.k + 2, "StagedInference")
-        assert len(example_inputs) == 1
-        dev = next(model.parameters()).device
-        self.device = dev
-        ex = example_inputs[0]['target_second_modality']
-        ldm = model.backbone.feature_extractor.ldm_extractor
-        self.ldm = ldm
+        ex = self._begin(model, example_inputs, self.k + 2)
+        dev = self.device
         self.s_enc = torch.cuda.Stream(device=dev, priority=-1)
         self.s_unet = [torch.cuda.Stream(device=dev) for _ in range(self.k)]
         self.s_dec = torch.cuda.Stream(device=dev)
-        self.static, self.graphs, self.outs, self.minmax = [], [], [], []
+        stages, probes = [], []
         cur = torch.cuda.current_stream(dev)
         with torch.no_grad(), ops.tuning_profile("throughput", pin=True):
             for j in range(self.n_slots):
                 stage_streams = [self.s_enc, self.s_unet[j % self.k], self.s_dec]
-                x = torch.empty(tuple(ex.shape), dtype=torch.float32, device=dev).copy_(ex)
-                call = [{'target_second_modality': x}]
+                call = self._static_call(ex)
                 for s in stage_streams:
                     s.wait_stream(cur)
                 self._run_staged(call, stage_streams, capture=False)      # sizes the three streams' workspaces outside the capture
                 torch.cuda.synchronize(dev)
                 out, graphs = self._run_staged(call, stage_streams, capture=True)
-                self.static.append(x)
-                self.graphs.append(graphs)
+                stages.append(list(zip(stage_streams, graphs)))
                 self.outs.append(out)
-                self.minmax.append(getattr(ldm, "last_minmax", None))
-        torch.cuda.synchronize(dev)
-        self.encoded = [torch.cuda.Event() for _ in range(self.n_slots)]
-        self.unet_done = [torch.cuda.Event() for _ in range(self.n_slots)]
-        self.done = [torch.cuda.Event() for _ in range(self.n_slots)]
-        self._ready = [torch.cuda.Event() for _ in range(2 * self.n_slots)]
-        self.turn = 0
-        if range_check is None:
-            range_check = bool(ldm.check_input_range)
-        self.range_check = DeferredRangeCheck(dev) if (range_check and self.minmax[0] is not None) else None
+                probes.append(getattr(self.ldm, "last_minmax", None))
+        self._arm(self.ldm, [self.s_enc, *self.s_unet, self.s_dec], stages, probes, range_check)
 
     def _run_staged(self, call, streams, capture):
         """One ``model(call)`` whose three stages run on ``streams`` (eager: chained by events) or are captured into three graphs."""
         ldm, dev = self.ldm, self.device
-        graphs, state = [], {"i": 0}
+        graphs, state = [], {"i": 0, "capturing": None}
         prev = torch.cuda.current_stream(dev)
 
         def begin(i):
@@ -484,11 +500,16 @@ class StagedInference:
                 g = torch.cuda.CUDAGraph()
                 g.capture_begin()
                 graphs.append(g)
+                state["capturing"] = g
+
+        def end():
+            g, state["capturing"] = state["capturing"], None
+            g.capture_end()
 
         def hook(_name):
             i = state["i"]
             if capture:
-                graphs[i].capture_end()
+                end()
             else:
                 ev = torch.cuda.Event()
                 ev.record(streams[i])
@@ -503,72 +524,20 @@ class StagedInference:
             out = self.model(call)
             assert state["i"] == 2, f"StagedInference: expected two stage boundaries in the forward, saw {state['i']}"
             if capture:
-                graphs[2].capture_end()
+                end()
         finally:
             ldm.__dict__["stage_hook"] = None
-            torch.cuda.set_stream(prev)
+            try:
+                if state["capturing"] is not None:     # the forward raised inside a stage: end its capture (on the stage's stream,
+                    end()                              # still current) and drop the partial graphs, as torch.cuda.graph.__exit__ does
+                    graphs.clear()
+            finally:
+                torch.cuda.set_stream(prev)
         if not capture:
             for s in streams:
                 s.synchronize()
         return out, graphs
 
-    @property
-    def streams_(self):
-        return [self.s_enc, *self.s_unet, self.s_dec]
-
     def stream_of(self, slot):
         """The stream the slot's LAST stage runs on: work enqueued there after ``submit`` is ordered behind the outputs."""
         return self.s_dec
-
-    def submit(self, batched_inputs):
-        """Returns ``Submitted`` = (outputs, event, slot); see ``GraphedInference.submit``."""
-        assert len(batched_inputs) == 1 and 'modality_type' not in batched_inputs[0]
-        if self.range_check is not None:
-            self.range_check.make_room()
-        j = self.turn % self.n_slots
-        first = self.turn < self.n_slots
-        turn = self.turn
-        self.turn += 1
-        x = batched_inputs[0]['target_second_modality']
-        assert tuple(x.shape) == tuple(self.static[j].shape), \
-            f"StagedInference: captured for images of shape {tuple(self.static[j].shape)}, got {tuple(x.shape)}"
-        if self.sync_inputs and x.is_cuda:
-            ready = self._ready[turn % len(self._ready)]
-            ready.record(torch.cuda.current_stream(self.device))
-        g1, g2, g3 = self.graphs[j]
-        with torch.cuda.stream(self.s_enc):
-            if self.sync_inputs and x.is_cuda:
-                self.s_enc.wait_event(ready)
-            if not first:
-                self.s_enc.wait_event(self.done[j])         # the slot's buffers (all three stages') are free again
-            self.static[j].copy_(x, non_blocking=True)
-            if x.is_cuda:
-                x.record_stream(self.s_enc)
-            taken = torch.cuda.Event()
-            taken.record(self.s_enc)
-            g1.replay()
-            self.encoded[j].record(self.s_enc)
-            if self.range_check is not None:
-                self.range_check.push(self.minmax[j], self.s_enc, turn)
-        su = self.s_unet[j % self.k]
-        with torch.cuda.stream(su):
-            su.wait_event(self.encoded[j])
-            g2.replay()
-            self.unet_done[j].record(su)
-        with torch.cuda.stream(self.s_dec):
-            self.s_dec.wait_event(self.unet_done[j])
-            g3.replay()
-            self.done[j].record(self.s_dec)
-        return Submitted((self.outs[j], self.done[j], j), taken, turn)
-
-    def drain(self):
-        for s in self.streams_:
-            s.synchronize()
-        if self.range_check is not None:
-            self.range_check.drain()
-
-    def quiesce(self):
-        for s in self.streams_:
-            s.synchronize()
-        if self.range_check is not None:
-            self.range_check.discard()

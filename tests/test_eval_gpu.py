@@ -378,6 +378,53 @@ def test_staged_inference_matches_forward(cuda):
     assert model.backbone.feature_extractor.ldm_extractor.__dict__.get("stage_hook") is None
 
 
+def test_staged_inference_capture_error_leaves_nothing_open(cuda):
+    """A host exception inside the model call WHILE a stage is being captured (here: the head, in the third stage, raises on its
+    second call -- the first is the eager warm-up run, the second the capture run; a Python exception between launches, nothing
+    happens on the device): the constructor re-raises it with the open stream capture ended, the stage hook removed and the
+    caller's stream current again, and a fresh runner on the same model works -- bit-identical to forward() as in
+    test_staged_inference_matches_forward."""
+    from madm_amd import ops
+    from madm_amd.pipeline import StagedInference
+    model = _build_product("DEPTH", torch.float16)
+    ldm = model.backbone.feature_extractor.ldm_extractor
+    g = torch.Generator().manual_seed(43)
+    calls = [[{"target_second_modality": (255.0 * torch.rand((3, 512, 512), generator=g)).cuda()}] for _ in range(3)]
+    head, calls_seen = model.sem_seg_head, []
+    head_forward = head.forward
+
+    def failing(*a, **k):
+        calls_seen.append(torch.cuda.is_current_stream_capturing())
+        if len(calls_seen) == 2:
+            raise RuntimeError("head failed on the host")
+        return head_forward(*a, **k)
+
+    before = torch.cuda.current_stream()
+    runner = StagedInference.__new__(StagedInference)        # keeps the streams reachable after the constructor raised
+    head.forward = failing
+    try:
+        with pytest.raises(RuntimeError, match="head failed on the host"):
+            runner.__init__(model, calls[0], unet_streams=2, slots=3)
+    finally:
+        del head.forward
+    assert calls_seen == [False, True]                       # it did raise inside the third stage's capture
+    for s in (runner.s_enc, *runner.s_unet, runner.s_dec):
+        with torch.cuda.stream(s):
+            assert not torch.cuda.is_current_stream_capturing()
+    assert ldm.__dict__["stage_hook"] is None
+    assert torch.cuda.current_stream() == before
+    runner = StagedInference(model, calls[0], unet_streams=2, slots=3)
+    got = []
+    for c in calls:
+        out, done, slot = runner.submit(c)
+        with torch.cuda.stream(runner.stream_of(slot)):
+            got.append(out[0]["sem_seg"].clone())
+    runner.drain()
+    with ops.tuning_profile("throughput", pin=True):         # the rows the stage graphs were captured under
+        for i, c in enumerate(calls):
+            assert torch.equal(got[i], model(c)[0]["sem_seg"]), f"image {i}: staged forward differs from forward()"
+
+
 def test_flat_adamw_ema_clip(cuda):
     """One-launch AdamW (+ folded unscale / clip) and EMA on flat fp32 storage against torch.optim.AdamW,
     clip_grad_norm_ and the reference's EMA formula (cmdise.py:337-349) on CPU."""

@@ -213,7 +213,7 @@ def test_staged_pipeline_matches_forward(extractor, slots):
         pipe.drain()
         assert pipe.range_check.checked == len(batches)
         if slots is None:
-            # the same batches from HOST memory (pinned image, pageable prompt tokens): copied in on the pipeline's transfer stream
+            # the same batches from HOST memory (pinned image, pageable prompt tokens): copied in on the pipeline's encoder stream
             for b in batches:
                 hb = {"img": b["img"].cpu().pin_memory(), "cond_inputs": b["cond_inputs"].cpu(), "cond_emb": b["cond_emb"]}
                 outs, done = pipe.submit(hb)
