@@ -22,7 +22,26 @@
  *   - `stream` is a hipStream_t passed as void*; all calls are asynchronous on it,
  *     capture-safe (no allocation, no synchronisation), re-entrant across streams;
  *   - return value: 0 = ok, negative = error (see madm_status); the message of the last
- *     error on the calling thread is returned by madm_last_error().
+ *     error on the calling thread is returned by madm_last_error();
+ *   - alignment: stated next to every pointer of the argument structs; a pointer or stride outside it is refused
+ *     (MADM_ERR_INVALID_ARG, nothing is launched).  The entry points that take plain pointers and require channel counts
+ *     and row strides in multiples of 16 bytes address those tensors in 16-byte chunks, so the tensors of `dtype` they
+ *     take must be 16-byte aligned: madm_groupnorm_stats / _apply / _apply_cat (x, x1, x2, y, residual), madm_groupnorm_bwd_*
+ *     (x, dy, dx, dres), madm_layernorm_fwd / _bwd (x, y, dy, dx, dres), madm_resize_bilinear (in, out), madm_dwconv3x3 (x, y),
+ *     madm_slide_merge (win, out), madm_scale_channels (x, y), madm_relu_bwd (y, dy, dx), madm_dwconv3x3_wgrad (x, dy),
+ *     madm_resize_bilinear_bwd (dout, din, workspace), madm_zero_insert2x / madm_sumpool2x2 (x, y), madm_colsum (x), madm_add
+ *     (a, b, y), madm_geglu_bwd (pre, dout, dpre), madm_stem_conv3x3 (out, wT, bias); madm_softmax_rows keeps 4 elements (s: 16
+ *     bytes, p: 8 in the 16-bit modes).  Three more groups are 16-byte aligned for the same reason: the f32 per-channel tables
+ *     of madm_dwconv3x3 (w, scale, shift: one of its kernels reads them as float4); the outputs that are written in whole
+ *     16-byte chunks up to Cpad / Kpad -- madm_image_to_nhwc / madm_image_to_im2col3x3 / madm_nchw_f32_to_nhwc (out),
+ *     madm_latents_add_noise (noisy) --; and the f32 image (img) of madm_image_to_nhwc / madm_image_to_im2col3x3 /
+ *     madm_stem_conv3x3 when minmax is given (the range probe reads it as float4; without minmax it is read element by
+ *     element).  The flat f32 kernels read float4 as well: madm_sumsq_f32 (x), madm_adamw_step /
+ *     madm_adamw_step_table (every buffer), madm_snapshot_f32 (src, dst; fingerprint 8 bytes), madm_mic_minmax (x; parts 8
+ *     bytes) are 16-byte aligned and refused otherwise.  An entry point not named in this list checks no alignment and needs
+ *     the element's own only.  A strided operand is a WINDOW: the kernels write nothing outside
+ *     [rows] x [columns] of an output and what they read outside an input never reaches a result
+ *     (tests/test_windows_gpu.py holds every entry point to that with live canaries around the windows).
  */
 #ifndef MADM_HIP_H
 #define MADM_HIP_H
@@ -85,30 +104,33 @@ int madm_calib_mfma_loop(int iters, int blocks, float* sink, double* flop, void*
  * ------------------------------------------------------------------------------- */
 typedef struct {
     int dtype;            /* madm_dtype */
-    const void* in1;      /* [B, IH, IW, C1] (pixel stride ld1); 16-byte aligned, < 2 GiB */
-    const void* in2;      /* [B, IH, IW, C2] or NULL when C2 == 0 */
+    const void* in1;      /* [B, IH, IW, C1] (pixel stride ld1); 16-byte aligned (read in 16-byte chunks), < 2 GiB */
+    const void* in2;      /* [B, IH, IW, C2] or NULL when C2 == 0; 16-byte aligned */
     int C1, C2;           /* multiples of the K-tile: 64 (bf16) / 32 (f32) elements */
-    int ld1, ld2;         /* pixel (row) strides of the sources in elements; 0 = dense (C1 / C2) */
+    int ld1, ld2;         /* pixel (row) strides of the sources in elements; 0 = dense (C1 / C2); multiples of 16 bytes */
     int B, IH, IW;        /* source dims (before the optional 2x upsample) */
     int OH, OW;
     int KH, KW;           /* 1x1 or 3x3 (any odd size works) */
     int stride;
     int pad_t, pad_l;     /* bottom/right padding is implied by OH/OW (zero fill) */
     int upsample;         /* 1: nearest 2x upsample of the sources before the conv */
-    const void* w;        /* [N][K] of dtype, K = KH*KW*(C1+C2) */
-    int ldw;              /* row stride of w in elements; 0 = dense (K) */
+    const void* w;        /* [N][K] of dtype, K = KH*KW*(C1+C2); 16-byte aligned */
+    int ldw;              /* row stride of w in elements; 0 = dense (K); a multiple of 16 bytes */
     int N;                /* output channels; multiple of 4 */
-    const float* bias;    /* [N] or NULL */
-    const float* rowvec;  /* [B][ldrv] or NULL: per-image row added to every pixel */
+    const float* bias;    /* [N] or NULL; 16-byte aligned (read as float4) */
+    const float* rowvec;  /* [B][ldrv] or NULL: per-image row added to every pixel; 16-byte aligned */
     int ldrv;             /* row stride of rowvec in floats (>= N, multiple of 4) */
-    const void* residual; /* [M][ldr] of dtype or NULL; added after the epilogue */
-    int ldr;
-    void* out;            /* [M][ldo] of dtype (f32 when out_f32), M = B*OH*OW */
-    int ldo;
+    const void* residual; /* [M][ldr] of dtype or NULL; added after the epilogue; aligned like out */
+    int ldr;              /* a multiple of 4 elements (2 under MADM_EPI_GEGLU) */
+    void* out;            /* [M][ldo] of dtype (f32 when out_f32), M = B*OH*OW; aligned to 4 elements of its type (2 under
+                           * MADM_EPI_GEGLU): 8 bytes in the 16-bit modes, 16 bytes for f32.  (The 16 x 16-patch kernel moves
+                           * 16-byte pieces of 16-bit out / residual when ldo, ldr, N are multiples of 8 AND both pointers are
+                           * 16-byte aligned, 8-byte pieces otherwise: same values either way.) */
+    int ldo;              /* a multiple of 4 elements (2 under MADM_EPI_GEGLU) */
     int out_f32;          /* 1: store f32 whatever the compute dtype (attention logits of the GEMM-based
                            * VAE mid-block attention); plain epilogue, no residual */
     int epilogue;         /* madm_epilogue */
-    double* stats;        /* NULL, or f64 [B][N][2], zeroed by the caller: receives the per-(image, channel)
+    double* stats;        /* NULL, or f64 [B][N][2] (8-byte aligned), zeroed by the caller: receives the per-(image, channel)
                            * sum and sum of squares of the stored output -- the statistics pass of the
                            * GroupNorm that consumes this tensor, fused into the producer's epilogue */
     /* fused GroupNorm(+act) of the INPUT (3x3 / stride 1 / pad 1 convs on maps >= 8x16 only, see
@@ -118,7 +140,8 @@ typedef struct {
      * y = act((x - mean_g) * rstd_g * gn_gamma[c] + gn_beta[c]) while staging its LDS halo tile, zero padding after
      * the activation.  gn_sums1 NULL = off; gn_groups <= 32 and divides C1 + C2; gn_gamma / gn_beta f32 [C1 + C2];
      * gn_act: madm_act (SiLU: ResnetBlock2D norm1/norm2 + nonlinearity, conv_norm_out + conv_act; ReLU: d2
-     * BottleneckBlock conv1.norm + relu before its 3x3 conv2) */
+     * BottleneckBlock conv1.norm + relu before its 3x3 conv2).  gn_sums1 / gn_sums2: 8-byte aligned; gn_gamma / gn_beta:
+     * 16-byte aligned */
     const double* gn_sums1;
     const double* gn_sums2;
     const float* gn_gamma;
@@ -127,7 +150,7 @@ typedef struct {
     float gn_eps;
     int gn_act;
     int splitk;           /* >=1; >1 needs workspace (f32 [splitk][M][N]) */
-    void* workspace;
+    void* workspace;      /* 16-byte aligned */
     size_t workspace_bytes;
     /* LayerNorm of the INPUT rows folded into a linear layer (ABI 2; diffusers BasicTransformerBlock norm1 -> attn1
      * to_q/k/v, norm2 -> attn2.to_q, norm3 -> ff.net.0.proj, modeling/meta_arch/ldm_diffusers.py:454-616 runs them as
@@ -136,7 +159,7 @@ typedef struct {
      * every row from the operand fragments it reads anyway and stores
      *     out[m][n] = rstd_m * (sum_k x[m][k] W'[n][k] - mean_m * ln_colsum[n]) + bias[n]    (then the epilogue)
      * == Linear(LayerNorm(x)); no separate normalisation pass, no re-read.  NULL = off.  Needs KH = KW = 1, one source,
-     * splitk == 1 (every workgroup walks whole rows), no fused GroupNorm. */
+     * splitk == 1 (every workgroup walks whole rows), no fused GroupNorm.  ln_colsum: 16-byte aligned. */
     const float* ln_colsum;
     float ln_eps;
     /* GroupNorm(+act) of the OUTPUT applied by the split-K reduction (ABI 3; diffusers ResnetBlock2D conv1 -> norm2 ->
@@ -145,7 +168,7 @@ typedef struct {
      * variance from them and stores out = act((v - mean) * rstd * pn_gamma[n] + pn_beta[n]): the raw conv output never
      * reaches memory and the stand-alone reduction + GroupNorm passes become one launch.  pn_gamma NULL = off.  Needs the
      * effective splitk > 1, the plain epilogue, no residual / stats / out_f32, N / pn_groups even and the group's values
-     * within 96 KB of LDS (madm_conv2d_plan.post_gn tells). */
+     * within 96 KB of LDS (madm_conv2d_plan.post_gn tells).  pn_gamma / pn_beta: 16-byte aligned. */
     const float* pn_gamma;
     const float* pn_beta;
     int pn_groups;
@@ -235,8 +258,11 @@ int madm_layernorm_fwd(int dtype, const void* x, void* y, int M, int C,
  * ------------------------------------------------------------------------------- */
 typedef struct {
     int dtype;
-    const void* q; const void* k; const void* v; void* o;
-    int ldq, ldk, ldv, ldo;   /* row strides in elements */
+    const void* q; const void* k; const void* v;   /* 16-byte aligned (read in 16-byte chunks) */
+    void* o;                  /* 8-byte aligned (8-byte stores) */
+    int ldq, ldk, ldv, ldo;   /* row strides in elements: ldq / ldk / ldv multiples of 16 bytes, ldo of 8 bytes; D * element size
+                               * a multiple of 16 bytes.  (madm_causal_attention_fwd reads and writes single floats: any
+                               * stride >= H * D, 4-byte alignment.) */
     int B, H, Lq, Lk, D;
     float scale;
 } madm_attention_args;
@@ -249,12 +275,12 @@ int madm_attention_fwd(const madm_attention_args* a, void* stream);
  * dk + dv), no atomics: deterministic.  D in {40, 64, 80, 160}. */
 typedef struct {
     int dtype;
-    const void* q; const void* k; const void* v; const void* o; const void* dout;
-    void* dq; void* dk; void* dv;
-    int ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;   /* row strides in elements */
+    const void* q; const void* k; const void* v; const void* o; const void* dout;   /* 16-byte aligned */
+    void* dq; void* dk; void* dv;                                                   /* 8-byte aligned */
+    int ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;   /* row strides in elements: multiples of 16 bytes (lddq / lddk / lddv: 8) */
     int B, H, Lq, Lk, D;
     float scale;
-    void* workspace;
+    void* workspace;          /* f32, 4-byte aligned */
     size_t workspace_bytes;
 } madm_attention_bwd_args;
 size_t madm_attention_bwd_workspace_bytes(const madm_attention_bwd_args* a);
@@ -396,17 +422,21 @@ int madm_argmax_nchw_f32(const float* x, int64_t* out, int B, int K, size_t HW, 
  * ------------------------------------------------------------------------------- */
 typedef struct {
     int dtype;            /* madm_dtype of in1 / in2 / dout */
-    const void* in1;      /* forward input [B, IH, IW, C1] (pixel stride ld1) */
-    const void* in2;      /* second source or NULL */
+    const void* in1;      /* forward input [B, IH, IW, C1] (pixel stride ld1); 16-byte aligned */
+    const void* in2;      /* second source or NULL; 16-byte aligned */
     int C1, C2;           /* multiples of 8 (bf16) / 4 (f32) elements */
-    int ld1, ld2;         /* 0 = dense */
-    const void* dout;     /* [M][ldd], M = B*OH*OW: gradient of the forward output */
-    int ldd;              /* 0 = dense (N) */
-    float* dw;            /* f32 [N][KH*KW*(C1+C2)], accumulated into */
+    int ld1, ld2;         /* 0 = dense; multiples of 16 bytes */
+    const void* dout;     /* [M][ldd], M = B*OH*OW: gradient of the forward output; aligned to 4 elements (8 bytes in the 16-bit
+                           * modes, 16 for f32).  It is read in 16-byte chunks: where N is not a multiple of the chunk the last
+                           * chunk of a row covers up to 4 elements of what follows the window; they only feed rows n >= N of
+                           * the product, which are never stored */
+    int ldd;              /* 0 = dense (N); a multiple of 4 elements */
+    float* dw;            /* f32 [N][KH*KW*(C1+C2)] dense, accumulated into (float atomics: 4-byte aligned) */
     int B, IH, IW, OH, OW, KH, KW, stride, pad_t, pad_l, upsample;
     int N;                /* multiple of 4 */
     int splitm;           /* pixel slices; 0 = choose for the MI355X grid */
-    float* dbias;         /* NULL or f32 [N], accumulated into: sum over the M rows of dout (nn.Conv2d / nn.Linear bias.grad) */
+    float* dbias;         /* NULL or f32 [N] (4-byte aligned), accumulated into: sum over the M rows of dout (nn.Conv2d / nn.Linear
+                           * bias.grad) */
 } madm_conv2d_wgrad_args;
 int madm_conv2d_wgrad(const madm_conv2d_wgrad_args* a, void* stream);
 int madm_pack_dgrad_weights(int dtype, const void* w, void* wt, int N, int taps, int C, void* stream);
@@ -464,7 +494,8 @@ int madm_layernorm_bwd(int dtype, const void* x, const void* dy, void* dx, int M
                        float* dgamma, float* dbeta, const void* dres, void* stream);
 /* GEGLU backward (diffusers GEGLU inside BasicTransformerBlock.ff): pre [M][N2] are the dense pre-activation rows of
  * the GEGLU GEMM in its interleaved (value_j, gate_j) order (madm_conv2d_fwd with MADM_EPI_NONE on the same packed
- * weights), dout [M][N2 / 2] the gradient of value * gelu_erf(gate); dpre [M][N2] in the same interleaved order. */
+ * weights), dout [M][N2 / 2] the gradient of value * gelu_erf(gate); dpre [M][N2] in the same interleaved order.
+ * pre / dout / dpre: dense, 16-byte aligned (16-byte chunks of pre / dpre; N2 a multiple of one chunk). */
 int madm_geglu_bwd(int dtype, const void* pre, const void* dout, void* dpre, size_t M, int N2, void* stream);
 
 /* ---------------------------------------------------------------------------------

@@ -173,7 +173,7 @@ SYMBOLS = [
     ("madm_snapshot_f32", c_int, [c_void_p, c_void_p, c_size_t, ctypes.c_ulonglong, c_void_p, c_void_p]),
     ("madm_label_to_rgb", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     ("madm_pseudo_label", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
-    ("madm_label_presence", c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("madm_label_presence", c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
     ("madm_class_mix", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
     ("madm_nchw_f32_to_nhwc", c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -473,6 +473,8 @@ extern "C" int madm_attention_fwd(const madm_attention_args* a, void* stream) {
     MADM_REQUIRE((a->ldq * es) % 16 == 0 && (a->ldk * es) % 16 == 0 && (a->ldv * es) % 16 == 0 &&
                      (a->ldo * es) % 8 == 0,
                  "attention: row strides must keep 16-byte alignment");
+    MADM_REQUIRE((((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v) & 15) == 0 && ((uintptr_t)a->o & 7) == 0,
+                 "attention: q / k / v must be 16-byte aligned (16-byte chunks), o 8-byte aligned (8-byte stores)");
     AttnP p;
     p.q = (const char*)a->q; p.k = (const char*)a->k; p.v = (const char*)a->v; p.o = (char*)a->o;
     p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;

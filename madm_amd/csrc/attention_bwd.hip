@@ -303,6 +303,9 @@ extern "C" int madm_attention_bwd(const madm_attention_bwd_args* a, void* stream
                      (a->ldo * es) % 16 == 0 && (a->lddo * es) % 16 == 0 && (a->lddq * es) % 8 == 0 &&
                      (a->lddk * es) % 8 == 0 && (a->lddv * es) % 8 == 0,
                  "attention_bwd: row strides must keep 16-byte (gradients: 8-byte) alignment");
+    MADM_REQUIRE((((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o | (uintptr_t)a->dout) & 15) == 0 &&
+                     (((uintptr_t)a->dq | (uintptr_t)a->dk | (uintptr_t)a->dv) & 7) == 0 && ((uintptr_t)a->workspace & 3) == 0,
+                 "attention_bwd: q / k / v / o / dout must be 16-byte aligned, dq / dk / dv 8-byte aligned, the workspace 4-byte");
     MADM_REQUIRE(a->workspace && a->workspace_bytes >= madm_attention_bwd_workspace_bytes(a),
                  "attention_bwd: workspace of %zu bytes needed", madm_attention_bwd_workspace_bytes(a));
     AttnBwdP p;

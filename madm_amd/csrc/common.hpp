@@ -17,6 +17,12 @@ static inline int madm_epc(int dtype) { return dtype == MADM_F32 ? 4 : 8; }
 static inline int madm_esize(int dtype) { return dtype == MADM_F32 ? 4 : 2; }
 static inline bool madm_dtype_ok(int dtype) { return dtype == MADM_F32 || dtype == MADM_BF16 || dtype == MADM_F16; }
 
+// true when every given pointer is 16-byte aligned: the tensors the kernels address in 16-byte chunks (NULL = an absent operand)
+static inline bool madm_aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+             reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+
 void madm_set_error(const char* fmt, ...);
 int madm_check_launch(const char* what);
 

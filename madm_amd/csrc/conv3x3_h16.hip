@@ -616,7 +616,11 @@ int launch_conv3x3_h16(const IgemmP& p, int bn, hipStream_t s) {
     (void)bn;
     if (p.splitk > 1) return fuse ? launch_h16_one<T, 128, true, false, true>(p, s) : launch_h16_one<T, 128, false, false, true>(p, s);
     if constexpr (sizeof(T) == 2) {
-        if (p.splitk == 1 && !p.out_f32 && p.epilogue != MADM_EPI_GEGLU && (p.ldo & 7) == 0 && (p.N & 7) == 0)
+        // the 16-byte path moves whole chunks of out (stores) and residual (LDS-DMA): rows AND base pointers must keep 16-byte
+        // alignment; the contract of out / residual is 8 bytes (madm_hip.h), anything less aligned takes the direct path
+        const bool rows16 = (p.ldo & 7) == 0 && (p.N & 7) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0 &&
+                            (!p.residual || ((p.ldr & 7) == 0 && (reinterpret_cast<uintptr_t>(p.residual) & 15) == 0));
+        if (p.splitk == 1 && !p.out_f32 && p.epilogue != MADM_EPI_GEGLU && rows16)
             return fuse ? launch_h16_one<T, 128, true, true>(p, s) : launch_h16_one<T, 128, false, true>(p, s);
     }
     return fuse ? launch_h16_one<T, 128, true, false>(p, s) : launch_h16_one<T, 128, false, false>(p, s);

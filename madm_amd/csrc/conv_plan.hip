@@ -254,6 +254,23 @@ int fill_params(const Request& r, IgemmP& p) {
     }
     p.nk = r.k_steps();
     MADM_REQUIRE((long long)p.nk * (std::min(a->splitk, p.nk) + 1) < 0x7fffffffLL, "conv2d: K too large for the 32-bit slice arithmetic");
+    // Alignment (include/madm_hip.h states it next to every field).  Sources and weights are read in 16-byte chunks (registers or
+    // LDS-DMA); bias / rowvec / ln_colsum and the GroupNorm parameters as float4; out and residual in units of 4 elements (2 under
+    // GEGLU) -- 8 bytes in the 16-bit modes, where only the 16 x 16-patch kernel's LDS-transposed path moves 16 bytes and looks
+    // at the pointers itself (launch_conv3x3_h16); the statistics are f64 atomics.
+    {
+        auto al = [](const void* q, size_t n) { return (reinterpret_cast<uintptr_t>(q) & (n - 1)) == 0; };
+        const size_t ounit = (a->epilogue == MADM_EPI_GEGLU ? 2 : 4) * (a->out_f32 ? 4 : madm_esize(a->dtype));
+        const size_t runit = (a->epilogue == MADM_EPI_GEGLU ? 2 : 4) * madm_esize(a->dtype);
+        MADM_REQUIRE(al(a->in1, 16) && al(a->in2, 16) && al(a->w, 16), "conv2d: in1 / in2 / w must be 16-byte aligned");
+        MADM_REQUIRE(al(a->bias, 16) && al(a->rowvec, 16) && al(a->ln_colsum, 16) && al(a->gn_gamma, 16) && al(a->gn_beta, 16) &&
+                     al(a->pn_gamma, 16) && al(a->pn_beta, 16) && al(a->workspace, 16),
+                     "conv2d: bias / rowvec / ln_colsum / gn_* / pn_* parameters and the workspace must be 16-byte aligned");
+        MADM_REQUIRE(al(a->stats, 8) && al(a->gn_sums1, 8) && al(a->gn_sums2, 8), "conv2d: f64 statistics must be 8-byte aligned");
+        MADM_REQUIRE(al(a->out, ounit), "conv2d: out must be aligned to %zu bytes", ounit);
+        MADM_REQUIRE(!a->residual || (al(a->residual, runit) && (a->epilogue == MADM_EPI_GEGLU || a->ldr % 4 == 0)),
+                     "conv2d: residual must be aligned to %zu bytes and ldr a multiple of 4 (2 under GEGLU)", runit);
+    }
     return MADM_OK;
 }
 

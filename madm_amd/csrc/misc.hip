@@ -512,6 +512,8 @@ int madm_image_to_nhwc(int dtype, const float* img, void* out, int B, int C, int
     MADM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && Cpad >= C && Cpad % epc == 0,
                  "image_to_nhwc: bad dims (C=%d Cpad=%d)", C, Cpad);
     MADM_REQUIRE(std != 0.f, "image_to_nhwc: std == 0");
+    MADM_REQUIRE(madm_aligned16(out) && (!minmax || madm_aligned16(img)),
+                 "image_to_nhwc: out (16-byte chunks) and, with minmax, img (float4 loads) must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const size_t total = (size_t)B * H * W;
     MADM_DISPATCH_DTYPE(dtype, (image_to_nhwc_kernel<T><<<grid_for(total), 256, 0, s>>>(
@@ -526,6 +528,8 @@ int madm_image_to_im2col3x3(int dtype, const float* img, void* out, int B, int H
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(B > 0 && H > 0 && W > 0 && Kpad >= 27 && Kpad % epc == 0, "image_to_im2col3x3: bad dims");
     MADM_REQUIRE(std != 0.f, "image_to_im2col3x3: std == 0");
+    MADM_REQUIRE(madm_aligned16(out) && (!minmax || madm_aligned16(img)),
+                 "image_to_im2col3x3: out (16-byte chunks) and, with minmax, img (float4 loads) must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     MADM_REQUIRE(Kpad >= 32, "image_to_im2col3x3: Kpad must be at least 32");
     const size_t total = (size_t)B * H * W;
@@ -542,6 +546,8 @@ int madm_stem_conv3x3(int dtype, const float* img, const float* wT, const float*
     MADM_REQUIRE(madm_dtype_ok(dtype), "stem_conv3x3: bad dtype");
     MADM_REQUIRE(N == STEM_N, "stem_conv3x3: N = %d, this kernel is the SD VAE stem (N = %d)", N, STEM_N);
     MADM_REQUIRE(B > 0 && H > 0 && W > 0 && ldo >= N && ldo % 4 == 0 && std != 0.f, "stem_conv3x3: bad dims");
+    MADM_REQUIRE(madm_aligned16(out, wT, bias), "stem_conv3x3: out / wT / bias must be 16-byte aligned (16-byte stores, float4 loads)");
+    MADM_REQUIRE(!minmax || madm_aligned16(img), "stem_conv3x3: with minmax, img must be 16-byte aligned (float4 loads)");
     const size_t nblocks = (size_t)B * ((H + STEM_ROWS - 1) / STEM_ROWS) * ((W + STEM_SEG - 1) / STEM_SEG);
     MADM_REQUIRE(nblocks < 0x7fffffffull, "stem_conv3x3: grid too large");
     hipStream_t s = (hipStream_t)stream;
@@ -573,6 +579,7 @@ int madm_latents_add_noise(int dtype, const void* moments, int ldm, float scalin
     MADM_REQUIRE(moments && noise && sqrt_ac && sqrt_1mac && timesteps && noisy, "latents_add_noise: null pointer");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(B > 0 && HW > 0 && ldm >= 4 && Cpad >= 4 && Cpad % epc == 0, "latents_add_noise: bad dims");
+    MADM_REQUIRE(madm_aligned16(noisy), "latents_add_noise: noisy must be 16-byte aligned (16-byte chunks)");
     hipStream_t s = (hipStream_t)stream;
     MADM_DISPATCH_DTYPE(dtype, (latents_add_noise_kernel<T><<<grid_for((size_t)B * HW), 256, 0, s>>>(
                                    (const T*)moments, ldm, scaling, noise, sqrt_ac, sqrt_1mac, timesteps,

@@ -355,6 +355,8 @@ int madm_softmax_rows(int dtype, const float* s, void* p, int rows, int L, int l
     MADM_REQUIRE(s && p && rows > 0 && L > 0 && L % 4 == 0 && lds >= L && ldp >= L && lds % 4 == 0 && ldp % 4 == 0,
                  "softmax_rows: bad args");
     MADM_REQUIRE(L <= 64 * 4 * 16, "softmax_rows: L=%d too long (max 4096)", L);
+    MADM_REQUIRE(madm_dtype_ok(dtype) && madm_aligned16(s) && (reinterpret_cast<uintptr_t>(p) & (4 * madm_esize(dtype) - 1)) == 0,
+                 "softmax_rows: s must be 16-byte aligned, p aligned to 4 elements");
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)((rows + 3) / 4));
     const float sl2 = scale * 1.44269504088896340736f;
@@ -365,6 +367,7 @@ int madm_softmax_rows(int dtype, const float* s, void* p, int rows, int L, int l
 
 int madm_groupnorm_stats(int dtype, const void* x, int B, int HW, int C, double* chsums, void* stream) {
     MADM_REQUIRE(x && chsums, "groupnorm_stats: null pointer");
+    MADM_REQUIRE(madm_aligned16(x), "groupnorm_stats: x must be 16-byte aligned (16-byte chunks)");
     MADM_REQUIRE(B > 0 && HW > 0 && C > 0, "groupnorm_stats: bad dims B=%d HW=%d C=%d", B, HW, C);
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(C % epc == 0, "groupnorm_stats: C=%d must be a multiple of %d", C, epc);
@@ -387,6 +390,7 @@ int madm_groupnorm_apply(int dtype, const void* x, void* y, int ldy, int B, int 
                          int G, const double* sums1, int C1, const double* sums2, const float* gamma,
                          const float* beta, float eps, int act, const void* residual, int ldres, void* stream) {
     MADM_REQUIRE(x && y && sums1 && gamma && beta, "groupnorm_apply: null pointer");
+    MADM_REQUIRE(madm_aligned16(x, y, residual), "groupnorm_apply: x / y / residual must be 16-byte aligned (16-byte chunks)");
     MADM_REQUIRE(B > 0 && HW > 0 && C > 0 && G > 0 && Ctot % G == 0 && c_off >= 0 && c_off + C <= Ctot && ldy >= c_off + C,
                  "groupnorm_apply: bad dims");
     MADM_REQUIRE(C1 > 0 && C1 <= Ctot && (C1 == Ctot || sums2), "groupnorm_apply: bad statistics sources (C1=%d Ctot=%d)", C1, Ctot);
@@ -413,6 +417,7 @@ int madm_groupnorm_apply_cat(int dtype, const void* x1, const void* x2, void* y,
                              int G, const double* sums1, const double* sums2, const float* gamma, const float* beta,
                              float eps, int act, void* stream) {
     MADM_REQUIRE(x1 && x2 && y && sums1 && sums2 && gamma && beta, "groupnorm_apply_cat: null pointer");
+    MADM_REQUIRE(madm_aligned16(x1, x2, y), "groupnorm_apply_cat: x1 / x2 / y must be 16-byte aligned (16-byte chunks)");
     const int Ctot = C1 + C2;
     MADM_REQUIRE(B > 0 && HW > 0 && C1 > 0 && C2 > 0 && G > 0 && Ctot % G == 0 && ldy >= Ctot, "groupnorm_apply_cat: bad dims");
     const int epc = madm_epc(dtype);
@@ -448,6 +453,7 @@ int madm_groupnorm_finalize(int B, int HW, int Ctot, int G, const double* sums1,
 int madm_layernorm_fwd(int dtype, const void* x, void* y, int M, int C, const float* gamma, const float* beta,
                        float eps, void* stream) {
     MADM_REQUIRE(x && y && gamma && beta, "layernorm: null pointer");
+    MADM_REQUIRE(madm_aligned16(x, y), "layernorm: x / y must be 16-byte aligned (16-byte chunks)");
     MADM_REQUIRE(M > 0 && C > 0, "layernorm: bad dims");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(C % epc == 0, "layernorm: C=%d must be a multiple of %d", C, epc);

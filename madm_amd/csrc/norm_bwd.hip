@@ -407,6 +407,7 @@ int gn_bwd_check(int dtype, const void* x, const void* dy, int lddy, int B, int 
                  const double* bsums, size_t lds_floats) {
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(x && dy && sums1 && gamma && beta && bsums, "groupnorm_bwd: null argument");
+    MADM_REQUIRE(madm_aligned16(x, dy), "groupnorm_bwd: x / dy must be 16-byte aligned (16-byte chunks)");
     MADM_REQUIRE(B > 0 && HW > 0 && C > 0 && C % epc == 0 && lddy % epc == 0 && c_off % epc == 0,
                  "groupnorm_bwd: C / lddy / c_off must be multiples of %d elements", epc);
     MADM_REQUIRE(G > 0 && Ctot % G == 0 && c_off >= 0 && c_off + C <= Ctot && C1 > 0 && C1 <= Ctot &&
@@ -450,6 +451,7 @@ int madm_groupnorm_bwd_apply(int dtype, const void* x, const void* dy, int lddy,
                                 (size_t)6 * C);
     if (rc != MADM_OK) return rc;
     MADM_REQUIRE(dx && (!dgamma == !dbeta), "groupnorm_bwd_apply: dx missing or only one of dgamma / dbeta given");
+    MADM_REQUIRE(madm_aligned16(dx, dres), "groupnorm_bwd_apply: dx / dres must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(!dres || lddres % epc == 0, "groupnorm_bwd_apply: lddres must be a multiple of %d elements", epc);
     // a block covers rowlanes rows per step (threads = column chunks x row lanes) and every thread takes four rows per
@@ -471,6 +473,7 @@ int madm_groupnorm_bwd_apply(int dtype, const void* x, const void* dy, int lddy,
 
 int madm_geglu_bwd(int dtype, const void* pre, const void* dout, void* dpre, size_t M, int N2, void* stream) {
     MADM_REQUIRE(pre && dout && dpre && M > 0 && N2 > 0, "geglu_bwd: bad argument");
+    MADM_REQUIRE(madm_aligned16(pre, dout, dpre), "geglu_bwd: pre / dout / dpre must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(N2 % epc == 0, "geglu_bwd: 2N = %d must be a multiple of %d", N2, epc);
     const size_t chunks = M * (size_t)(N2 / epc);
@@ -484,6 +487,7 @@ int madm_geglu_bwd(int dtype, const void* pre, const void* dout, void* dpre, siz
 int madm_layernorm_bwd(int dtype, const void* x, const void* dy, void* dx, int M, int C, const float* gamma, float eps,
                        float* dgamma, float* dbeta, const void* dres, void* stream) {
     MADM_REQUIRE(x && dy && dx && gamma && M > 0 && C > 0, "layernorm_bwd: bad argument");
+    MADM_REQUIRE(madm_aligned16(x, dy, dx, dres), "layernorm_bwd: x / dy / dx / dres must be 16-byte aligned (16-byte chunks)");
     MADM_REQUIRE(!dgamma == !dbeta, "layernorm_bwd: dgamma and dbeta go together");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(C % epc == 0, "layernorm_bwd: C=%d must be a multiple of %d", C, epc);

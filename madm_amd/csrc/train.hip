@@ -600,6 +600,7 @@ extern "C" {
 int madm_scale_channels(int dtype, const void* x, int ldx, const float* scale, void* y, int ldy, int B, int HW, int C,
                         void* stream) {
     MADM_REQUIRE(x && scale && y && B > 0 && HW > 0 && C > 0, "scale_channels: bad argument");
+    MADM_REQUIRE(madm_aligned16(x, y), "scale_channels: x / y must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(C % epc == 0 && ldx % epc == 0 && ldy % epc == 0 && ldx >= C && ldy >= C,
                  "scale_channels: C / ld must be multiples of %d elements", epc);
@@ -620,6 +621,7 @@ int madm_bn_fold_stats(const double* chsums, int B, int C, double count, float m
 
 int madm_relu_bwd(int dtype, const void* y, const void* dy, void* dx, size_t n, void* stream) {
     MADM_REQUIRE(y && dy && dx && n > 0, "relu_bwd: bad argument");
+    MADM_REQUIRE(madm_aligned16(y, dy, dx), "relu_bwd: y / dy / dx must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(n % epc == 0, "relu_bwd: n must be a multiple of %d elements", epc);
     hipStream_t s = (hipStream_t)stream;
@@ -631,6 +633,7 @@ int madm_relu_bwd(int dtype, const void* y, const void* dy, void* dx, size_t n, 
 int madm_dwconv3x3_wgrad(int dtype, const void* x, const void* dy, int lddy, float* dw, int B, int H, int W, int C,
                          int dilation, void* stream) {
     MADM_REQUIRE(x && dy && dw && B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "dwconv3x3_wgrad: bad argument");
+    MADM_REQUIRE(madm_aligned16(x, dy), "dwconv3x3_wgrad: x / dy must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(C % epc == 0 && lddy % epc == 0 && lddy >= C, "dwconv3x3_wgrad: C / lddy must be multiples of %d", epc);
     hipStream_t s = (hipStream_t)stream;
@@ -674,6 +677,7 @@ int madm_resize_bilinear_bwd(int dtype, const void* dout, int lddo, void* din, i
                              void* workspace, size_t workspace_bytes, void* stream) {
     MADM_REQUIRE(dout && din && workspace && B > 0 && IH > 0 && IW > 0 && OH > 0 && OW > 0 && C > 0,
                  "resize_bilinear_bwd: bad argument");
+    MADM_REQUIRE(madm_aligned16(dout, din, workspace), "resize_bilinear_bwd: dout / din / workspace must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(C % epc == 0 && lddo % epc == 0 && lddo >= C, "resize_bilinear_bwd: C / lddo must be multiples of %d", epc);
     MADM_REQUIRE(workspace_bytes >= madm_resize_bilinear_bwd_workspace_bytes(B, IW, OH, C),

@@ -471,6 +471,7 @@ unsigned bwd_grid_for(size_t n) {
 extern "C" int madm_zero_insert2x(int dtype, const void* x, void* y, int B, int OH, int OW, int H, int W, int C,
                                   void* stream) {
     MADM_REQUIRE(x && y && B > 0 && OH > 0 && OW > 0 && H > 0 && W > 0 && C > 0, "zero_insert2x: bad argument");
+    MADM_REQUIRE(madm_aligned16(x, y), "zero_insert2x: x / y must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(madm_dtype_ok(dtype), "zero_insert2x: unknown dtype %d", dtype);
     MADM_REQUIRE(C % epc == 0, "zero_insert2x: C = %d must be a multiple of %d", C, epc);
@@ -482,6 +483,7 @@ extern "C" int madm_zero_insert2x(int dtype, const void* x, void* y, int B, int 
 
 extern "C" int madm_sumpool2x2(int dtype, const void* x, void* y, int B, int H, int W, int C, void* stream) {
     MADM_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0, "sumpool2x2: bad argument");
+    MADM_REQUIRE(madm_aligned16(x, y), "sumpool2x2: x / y must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(C % epc == 0, "sumpool2x2: C = %d must be a multiple of %d", C, epc);
     const size_t total = (size_t)B * H * W * (C / epc);
@@ -492,6 +494,7 @@ extern "C" int madm_sumpool2x2(int dtype, const void* x, void* y, int B, int H, 
 
 extern "C" int madm_colsum(int dtype, const void* x, int ldx, int B, int HW, int C, float* out, void* stream) {
     MADM_REQUIRE(x && out && B > 0 && HW > 0 && C > 0, "colsum: bad argument");
+    MADM_REQUIRE(madm_aligned16(x), "colsum: x must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(C % epc == 0 && ldx % epc == 0 && ldx >= C, "colsum: C / ldx must be multiples of %d elements", epc);
     int slices = (HW + 31) / 32;
@@ -507,6 +510,7 @@ extern "C" int madm_colsum(int dtype, const void* x, int ldx, int B, int HW, int
 
 extern "C" int madm_add(int dtype, const void* a, const void* b, void* y, size_t n, void* stream) {
     MADM_REQUIRE(a && b && y && n > 0, "add: bad argument");
+    MADM_REQUIRE(madm_aligned16(a, b, y), "add: a / b / y must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(n % epc == 0, "add: n must be a multiple of %d elements", epc);
     const size_t chunks = n / epc;
@@ -542,6 +546,12 @@ extern "C" int madm_conv2d_wgrad(const madm_conv2d_wgrad_args* a, void* stream) 
     p.ldd = a->ldd ? a->ldd : a->N;
     MADM_REQUIRE(p.ld1 % epc == 0 && p.ld2 % epc == 0 && p.ldd % 4 == 0, "conv2d_wgrad: row strides must keep 16-byte "
                  "(dout: 8-byte) alignment");
+    {   // the sources are read as 16-byte chunks at (pixel * ld + c) elements, dout as 16-byte chunks at rows that keep 4 elements
+        auto al = [](const void* q, size_t n) { return (reinterpret_cast<uintptr_t>(q) & (n - 1)) == 0; };
+        MADM_REQUIRE(al(a->in1, 16) && al(a->in2, 16), "conv2d_wgrad: in1 / in2 must be 16-byte aligned");
+        MADM_REQUIRE(al(a->dout, 4 * esz), "conv2d_wgrad: dout must be aligned to %zu bytes", 4 * esz);
+        MADM_REQUIRE(al(a->dw, 4) && al(a->dbias, 4), "conv2d_wgrad: dw / dbias must be 4-byte aligned");
+    }
     p.B = a->B; p.IH = a->IH; p.IW = a->IW; p.OH = a->OH; p.OW = a->OW; p.KH = a->KH; p.KW = a->KW;
     p.stride = a->stride; p.pad_t = a->pad_t; p.pad_l = a->pad_l; p.upsample = a->upsample ? 1 : 0;
     p.N = a->N; p.K = a->KH * a->KW * p.Ctot;
