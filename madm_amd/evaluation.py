@@ -34,6 +34,10 @@ class SemSegEvaluator:
             if self.convert_pred_list is not None:
                 raise NotImplementedError("convert_pred_list (d2_evaluator.py:108-112) is not used by the shipped configs")
             gt = data["target_label"]
+            if gt.is_cuda:
+                # read here, on the stream process was called under (a runner's slot stream), behind a whole forward: a device label
+                # that a loader produced on a stream of its own must not go back to that stream's pool before then
+                gt.record_stream(torch.cuda.current_stream(gt.device))
             if gt.dim() == 3 and gt.shape[0] == 1:
                 gt = gt[0]
             gt = gt.to(pred.device).long()
@@ -145,6 +149,8 @@ class DSECSemSegEvaluator(SemSegEvaluator):
         from .labels import _device_palette
         ex = self._exporter()
         image = data["target_second_modality"]
+        if image.is_cuda:
+            image.record_stream(torch.cuda.current_stream(image.device))      # as for the label in process
         if image.dim() == 4 and image.shape[0] == 1:
             image = image[0]
         image = image.to(pred.device)
