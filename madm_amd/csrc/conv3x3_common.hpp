@@ -103,7 +103,9 @@ __device__ __forceinline__ void gn_fold_affine(float2 st, float& sc, float& sh) 
 
 // ---- patch epilogue shared by the register-staged and the LDS-DMA halo kernels ----
 // lane: pixel = patch row wm*4+i, column frow; channels n .. n+3.  ``red`` = >= 4 * BN floats of LDS nobody reads any more.
-template <typename T, int BN>
+// PERM: the permuted channel mapping of igemm_tile_epilogue (igemm.hip) -- the LDS-DMA kernel fetches its weight rows in that order
+// and the lane's 4 * NI channels are contiguous; the register-staged kernel keeps the plain mapping.
+template <typename T, int BN, bool PERM = false>
 __device__ __forceinline__ void halo_tile_epilogue(const IgemmP& p, f32x4 (&acc)[4][BN / 32], int b, int py0, int px0,
                                                    int n0, int z, float* red) {
     constexpr int MI = 4, NI = BN / 32;
@@ -111,11 +113,13 @@ __device__ __forceinline__ void halo_tile_epilogue(const IgemmP& p, f32x4 (&acc)
     const int wm = wave >> 1, wn = wave & 1;
     const int frow = lane & 15, fg = lane >> 4;
     const bool want_stats = p.stats != nullptr && p.splitk == 1;
-    const int nb = n0 + wn * (BN / 2) + fg * 4;
+    constexpr int CS = PERM ? 4 : 16;
+    const int lb = wn * (BN / 2) + fg * (PERM ? 4 * NI : 4);
+    const int nb = n0 + lb;
     f32x4 cs[NI], cq[NI], add[NI];
 #pragma unroll
     for (int j = 0; j < NI; ++j) { cs[j] = f32x4{0.f, 0.f, 0.f, 0.f}; cq[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    if (p.splitk == 1) epilogue_consts<NI>(p, nb, b, add);   // a patch lies in one image
+    if (p.splitk == 1) epilogue_consts<NI, CS>(p, nb, b, add);   // a patch lies in one image
     int mrow[MI];
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
@@ -129,20 +133,20 @@ __device__ __forceinline__ void halo_tile_epilogue(const IgemmP& p, f32x4 (&acc)
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
                 const f32x4 v = acc[i][j];
-                if (nb + 16 * j < p.N)
-                    *reinterpret_cast<float4*>(p.ws + ((size_t)z * p.M + mrow[i]) * p.N + nb + 16 * j) =
+                if (nb + CS * j < p.N)
+                    *reinterpret_cast<float4*>(p.ws + ((size_t)z * p.M + mrow[i]) * p.N + nb + CS * j) =
                         make_float4(v[0], v[1], v[2], v[3]);
             }
         }
     } else {
-        epilogue_tile<T, MI, NI>(p, mrow, nb, add, false, acc);
+        epilogue_tile<T, MI, NI, CS>(p, mrow, nb, add, false, acc, PERM && EpiWide<T, NI>::ok(p));
         if (want_stats) {
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
                 if (mrow[i] < 0) continue;
 #pragma unroll
                 for (int j = 0; j < NI; ++j)
-                    if (nb + 16 * j < p.N) { cs[j] += acc[i][j]; cq[j] += acc[i][j] * acc[i][j]; }
+                    if (nb + CS * j < p.N) { cs[j] += acc[i][j]; cq[j] += acc[i][j] * acc[i][j]; }
             }
         }
     }
@@ -155,7 +159,7 @@ __device__ __forceinline__ void halo_tile_epilogue(const IgemmP& p, f32x4 (&acc)
                 cq[j][r] = row16_sum(cq[j][r]);
             }
             if (frow == 0) {
-                float* dst = red + ((wm * BN) + wn * (BN / 2) + j * 16 + fg * 4) * 2;
+                float* dst = red + ((wm * BN) + lb + CS * j) * 2;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { dst[2 * r] = cs[j][r]; dst[2 * r + 1] = cq[j][r]; }
             }

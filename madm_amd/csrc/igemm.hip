@@ -66,7 +66,10 @@ __device__ __forceinline__ void cstash_park(bool on, u32x4 cb_, u32x4 cr_, u32x4
 // in the f64 stats[B][N][2] (f32 partials per block, f64 atomics across blocks: reproducible to f32 rounding whatever
 // the arrival order) -- the consumer GroupNorm then needs no pass of its own.  ``red`` = >= 4 * BN floats of LDS that
 // no wave reads any more (the caller has passed a barrier since the last MFMA operand read).
-template <typename T, int BM, int BN>
+// PERM (igemm_glds_kernel's permuted weight rows): MFMA row m of channel tile j is channel (m >> 2) * (4 * NI) + 4 * j + (m & 3) of
+// the wave's span, so the lane's NI chunks are the 4 * NI CONSECUTIVE channels from fg * 4 * NI and leave in wide pieces
+// (epilogue_tile).  Per element the arithmetic and its order are those of the plain mapping: bit-identical outputs and statistics.
+template <typename T, int BM, int BN, bool PERM = false>
 __device__ __forceinline__ void igemm_tile_epilogue(const IgemmP& p, f32x4 (&acc)[BM / 32][BN / 32], int m0, int n0,
                                                     int z, float* red, float (&lns)[BM / 32], float (&lnq)[BM / 32],
                                                     const float* cstash, const float* cstash_row, const float* cstash_ln) {
@@ -79,7 +82,9 @@ __device__ __forceinline__ void igemm_tile_epilogue(const IgemmP& p, f32x4 (&acc
     int mlast = m0 + BM; if (mlast > p.M) mlast = p.M; mlast -= 1;
     const int img0 = m0 / OHW;
     const bool one_image = (mlast / OHW) == img0;   // block-uniform
-    const int nb = n0 + wn * (BN / 2) + fg * 4;
+    constexpr int CS = PERM ? 4 : 16;                            // channels between the lane's chunks j and j + 1
+    const int lb = wn * (BN / 2) + fg * (PERM ? 4 * NI : 4);     // the lane's first channel within the tile
+    const int nb = n0 + lb;
     f32x4 cs[NI], cq[NI], add[NI];
 #pragma unroll
     for (int j = 0; j < NI; ++j) { cs[j] = f32x4{0.f, 0.f, 0.f, 0.f}; cq[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -87,10 +92,10 @@ __device__ __forceinline__ void igemm_tile_epilogue(const IgemmP& p, f32x4 (&acc
                            // the LDS-DMA kernel parks the two rows separately (no adder on that path)
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
-            const float4 c = *reinterpret_cast<const float4*>(cstash + wn * (BN / 2) + fg * 4 + 16 * j);
+            const float4 c = *reinterpret_cast<const float4*>(cstash + lb + CS * j);
             add[j] = f32x4{c.x, c.y, c.z, c.w};
             if (cstash_row) {
-                const float4 r = *reinterpret_cast<const float4*>(cstash_row + wn * (BN / 2) + fg * 4 + 16 * j);
+                const float4 r = *reinterpret_cast<const float4*>(cstash_row + lb + CS * j);
                 add[j] += f32x4{r.x, r.y, r.z, r.w};
             }
         }
@@ -101,7 +106,7 @@ __device__ __forceinline__ void igemm_tile_epilogue(const IgemmP& p, f32x4 (&acc
         f32x4 csv[NI];
 #pragma unroll
         for (int j = 0; j < NI; ++j) {   // parked in LDS with the other epilogue constants
-            const float4 c = *reinterpret_cast<const float4*>(cstash_ln + wn * (BN / 2) + fg * 4 + 16 * j);
+            const float4 c = *reinterpret_cast<const float4*>(cstash_ln + lb + CS * j);
             csv[j] = f32x4{c.x, c.y, c.z, c.w};
         }
         const float inv_k = 1.0f / (float)p.K;
@@ -143,22 +148,22 @@ __device__ __forceinline__ void igemm_tile_epilogue(const IgemmP& p, f32x4 (&acc
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
                 const f32x4 v = acc[i][j];
-                if (nb + 16 * j < p.N)
-                    *reinterpret_cast<float4*>(p.ws + ((size_t)z * p.M + mrow[i]) * p.N + nb + 16 * j) =
+                if (nb + CS * j < p.N)
+                    *reinterpret_cast<float4*>(p.ws + ((size_t)z * p.M + mrow[i]) * p.N + nb + CS * j) =
                         make_float4(v[0], v[1], v[2], v[3]);
             }
         }
     } else {
-        epilogue_tile<T, MI, NI>(p, mrow, nb, add, !one_image, acc);
+        epilogue_tile<T, MI, NI, CS>(p, mrow, nb, add, !one_image, acc, PERM && EpiWide<T, NI>::ok(p));
         if (want_stats) {
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
                 if (mrow[i] < 0) continue;
 #pragma unroll
                 for (int j = 0; j < NI; ++j) {
-                    if (nb + 16 * j >= p.N) continue;
+                    if (nb + CS * j >= p.N) continue;
                     if (one_image) { cs[j] += acc[i][j]; cq[j] += acc[i][j] * acc[i][j]; }
-                    else stats_add_elementwise(p, mrow[i], nb + 16 * j, acc[i][j]);
+                    else stats_add_elementwise(p, mrow[i], nb + CS * j, acc[i][j]);
                 }
             }
         }
@@ -173,7 +178,7 @@ __device__ __forceinline__ void igemm_tile_epilogue(const IgemmP& p, f32x4 (&acc
                 cq[j][r] = row16_sum(cq[j][r]);
             }
             if (frow == 0) {
-                float* dst = red + ((wm * BN) + wn * (BN / 2) + j * 16 + fg * 4) * 2;
+                float* dst = red + ((wm * BN) + lb + CS * j) * 2;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { dst[2 * r] = cs[j][r]; dst[2 * r + 1] = cq[j][r]; }
             }
@@ -361,7 +366,8 @@ __device__ unsigned long long g_glds_stamps[2048];
 // LIN: 1x1 / stride 1 / no padding / no upsampling (every linear layer and 1x1 conv): output row m reads input row m, so
 // the gather needs no pixel arithmetic -- neither in the set-up (two integer divisions per staged row) nor per DMA
 // instruction (the address is row * ld + channel offset).
-template <typename T, int BM, int BN, int NS, bool LIN>
+// PERM: the permuted channel mapping of igemm_tile_epilogue (wide epilogue stores); false = MFMA row m of tile j is channel 16 j + m.
+template <typename T, int BM, int BN, int NS, bool LIN, bool PERM>
 __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? (NS == 2 ? 2 : 1) : (NS == 3 && BM == 64 ? 3 : 2)) void igemm_glds_kernel(const IgemmP p) {
 #if defined(__HIP_DEVICE_COMPILE__)   // LDS address-space casts and gfx asm: device pass only (the host needs the stub)
     kernarg_touch<5>();
@@ -409,7 +415,11 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? (NS == 2 ? 2 : 1) : (NS
                 IGEMM_ROW_DECODE(LIN, p, m, OHW, a_b[i], a_iy[i], a_ix[i])
             }
         } else {
-            const int n = n0 + row - BM;
+            // permuted mapping (igemm_tile_epilogue PERM), applied where the tile is FETCHED like the XOR swizzle: the lane that
+            // fills LDS row (wave half, j, m) asks for the weight row of the channel that MFMA row stands for -- the LDS image and
+            // the fragment reads do not change
+            const int r = row - BM, rr = r & (BN / 2 - 1);
+            const int n = n0 + (PERM ? (r - rr) + ((rr & 15) >> 2) * (4 * NI) + ((rr >> 4) << 2) + (rr & 3) : r);
             if (n < p.N) wvoff[i] = (unsigned)(((size_t)n * p.ldw + swz[i]) * sizeof(T));
         }
     }
@@ -574,7 +584,7 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? (NS == 2 ? 2 : 1) : (NS
 #undef GLDS_LOAD_TILE
     GLDS_BSTAMP(3);
     __syncthreads();   // every wave is done with the last tile: the LDS becomes the statistics scratch
-    igemm_tile_epilogue<T, BM, BN>(p, acc, m0, n0, z, reinterpret_cast<float*>(gsmem), lns, lnq, cstash, cstash + 256, cstash + 512);
+    igemm_tile_epilogue<T, BM, BN, PERM>(p, acc, m0, n0, z, reinterpret_cast<float*>(gsmem), lns, lnq, cstash, cstash + 256, cstash + 512);
     GLDS_BSTAMP(4);
 #endif
 }
@@ -741,10 +751,10 @@ __global__ __launch_bounds__(PGN_THREADS) void splitk_groupnorm_kernel(const Ige
     }
 }
 
-template <typename T, int BM, int BN, int NS, bool LIN>
+template <typename T, int BM, int BN, int NS, bool LIN, bool PERM>
 int launch_glds_v(const IgemmP& p, dim3 grid, hipStream_t s) {
     constexpr size_t lds = (size_t)NS * (BM + BN) * 128;
-    auto kern = igemm_glds_kernel<T, BM, BN, NS, LIN>;
+    auto kern = igemm_glds_kernel<T, BM, BN, NS, LIN, PERM>;
     static std::atomic<uint64_t> attr_done{0};
     if (int e = madm_raise_dynamic_lds(reinterpret_cast<const void*>(kern), (size_t)(lds), attr_done, "igemm (LDS-DMA)")) return e;
     kern<<<grid, 256, lds, s>>>(p);
@@ -756,7 +766,9 @@ int launch_glds_v(const IgemmP& p, dim3 grid, hipStream_t s) {
 template <typename T, int CODE, int BM, int BN, TileFamily F, int SLOTS>
 int launch_gemm_tile(const IgemmP& p, dim3 grid, hipStream_t s, bool lin) {
     if constexpr (F == GLDS) {
-        return lin ? launch_glds_v<T, BM, BN, SLOTS, true>(p, grid, s) : launch_glds_v<T, BM, BN, SLOTS, false>(p, grid, s);
+        if (igemm_wide_epi())
+            return lin ? launch_glds_v<T, BM, BN, SLOTS, true, true>(p, grid, s) : launch_glds_v<T, BM, BN, SLOTS, false, true>(p, grid, s);
+        return lin ? launch_glds_v<T, BM, BN, SLOTS, true, false>(p, grid, s) : launch_glds_v<T, BM, BN, SLOTS, false, false>(p, grid, s);
     } else if constexpr (F == IGEMM) {
         if constexpr (CODE == 2 || CODE == 3) {
             if (lin) {

@@ -194,7 +194,7 @@ __device__ __forceinline__ f32x4 epilogue_store(const IgemmP& p, int m, int n, f
 // tile lies in one image, img >= 0).  Loaded ONCE per lane before the row loop: inside it the compiler must assume the
 // output stores alias them and re-issued the loads for every row -- a full L2 round trip each, 9 000 of the 16 000
 // clocks of a 128 x 128 tile's epilogue (in-kernel stamps, tools/exp/stamps_block.py).
-template <int NI>
+template <int NI, int CS = 16>   // CS: see epilogue_row
 __device__ __forceinline__ void epilogue_consts(const IgemmP& p, int nb, int img, f32x4 (&add)[NI]) {
     // no per-lane condition around the loads (a lane past column N reads the last valid chunk instead -- its values are
     // never stored nor counted): behind exec masks every load got a vmcnt(0) of its own, NI dependent round trips
@@ -204,7 +204,7 @@ __device__ __forceinline__ void epilogue_consts(const IgemmP& p, int nb, int img
         float4 b[NI];
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
-            const int n = nb + 16 * j < p.N ? nb + 16 * j : p.N - 4;
+            const int n = nb + CS * j < p.N ? nb + CS * j : p.N - 4;
             b[j] = *reinterpret_cast<const float4*>(p.bias + n);
         }
 #pragma unroll
@@ -214,7 +214,7 @@ __device__ __forceinline__ void epilogue_consts(const IgemmP& p, int nb, int img
         float4 t[NI];
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
-            const int n = nb + 16 * j < p.N ? nb + 16 * j : p.N - 4;
+            const int n = nb + CS * j < p.N ? nb + CS * j : p.N - 4;
             t[j] = *reinterpret_cast<const float4*>(p.rowvec + (size_t)img * p.ldrv + n);
         }
 #pragma unroll
@@ -245,23 +245,24 @@ __device__ __forceinline__ float row16_sum(float x) {
     return x;
 }
 
-// One output pixel row of a wave tile: NI chunks of 4 channels at n = nb + 16 * j.  All residual loads are issued
+// One output pixel row of a wave tile: NI chunks of 4 channels at n = nb + CS * j (CS = 16: MFMA row = channel; CS = 4: the
+// permuted weight rows of igemm_glds_kernel, the lane's 4 * NI channels are contiguous).  All residual loads are issued
 // first and the NI stores leave back to back, so the (up to) four 32-byte pieces of one 128-byte output line reach
 // the L2 together (with a load -> store chain per chunk the L2 evicted half-written lines: 2x HBM write traffic
 // measured on the VAE ResNet convs).  ``add`` = epilogue_consts; ``img_rows``: the time row was NOT folded into add
 // (tile straddles images) and is fetched per row.  v[j] returns the stored values (fused statistics).
-template <typename T, int NI>
+template <typename T, int NI, int CS = 16>
 __device__ __forceinline__ void epilogue_row(const IgemmP& p, int m, int nb, const f32x4 (&add)[NI], bool img_rows,
                                              f32x4 (&v)[NI]) {
     const float* rv = (p.rowvec && img_rows) ? p.rowvec + (size_t)(m / (p.OH * p.OW)) * p.ldrv + nb : nullptr;
     if (p.epilogue == MADM_EPI_GEGLU) {
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
-            const int n = nb + 16 * j;
+            const int n = nb + CS * j;
             if (n >= p.N) continue;
             f32x4 t = v[j] + add[j];
             if (rv) {
-                const float4 q = *reinterpret_cast<const float4*>(rv + 16 * j);
+                const float4 q = *reinterpret_cast<const float4*>(rv + CS * j);
                 t[0] += q.x; t[1] += q.y; t[2] += q.z; t[3] += q.w;
             }
             float o0 = t[0] * gelu_erf_f(t[1]);
@@ -281,14 +282,14 @@ __device__ __forceinline__ void epilogue_row(const IgemmP& p, int m, int nb, con
         const T* rp = reinterpret_cast<const T*>(p.residual) + (size_t)m * p.ldr + nb;
 #pragma unroll
         for (int j = 0; j < NI; ++j)
-            r[j] = (nb + 16 * j < p.N) ? load4<T>(rp + 16 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+            r[j] = (nb + CS * j < p.N) ? load4<T>(rp + CS * j) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
-        if (nb + 16 * j >= p.N) continue;
+        if (nb + CS * j >= p.N) continue;
         v[j] += add[j];
         if (rv) {
-            const float4 t = *reinterpret_cast<const float4*>(rv + 16 * j);
+            const float4 t = *reinterpret_cast<const float4*>(rv + CS * j);
             v[j][0] += t.x; v[j][1] += t.y; v[j][2] += t.z; v[j][3] += t.w;
         }
         if (p.residual) v[j] += r[j];
@@ -301,27 +302,76 @@ __device__ __forceinline__ void epilogue_row(const IgemmP& p, int m, int nb, con
         float* op = reinterpret_cast<float*>(p.out) + (size_t)m * p.ldo + nb;
 #pragma unroll
         for (int j = 0; j < NI; ++j)
-            if (nb + 16 * j < p.N) store4<float>(op + 16 * j, v[j]);
+            if (nb + CS * j < p.N) store4<float>(op + CS * j, v[j]);
     } else {
         T* op = reinterpret_cast<T*>(p.out) + (size_t)m * p.ldo + nb;
 #pragma unroll
         for (int j = 0; j < NI; ++j)
-            if (nb + 16 * j < p.N) store4<T>(op + 16 * j, v[j]);
+            if (nb + CS * j < p.N) store4<T>(op + CS * j, v[j]);
     }
 }
+
+// 8 consecutive elements from / to two chunks of four: ONE 16-byte access in the 16-bit modes (the element conversions are
+// those of load4 / store4), two float4s in f32
+template <typename T> __device__ __forceinline__ void store8(T* p, f32x4 a, f32x4 b) {
+    if constexpr (sizeof(T) == 4) {
+        store4<T>(p, a);
+        store4<T>(p + 4, b);
+    } else {
+        const float f[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+        *reinterpret_cast<uint4*>(p) = f32_to_chunk<T>(f);
+    }
+}
+template <typename T> __device__ __forceinline__ void load8(const T* p, f32x4& a, f32x4& b) {
+    if constexpr (sizeof(T) == 4) {
+        a = load4<T>(p);
+        b = load4<T>(p + 4);
+    } else {
+        float f[8];
+        chunk_to_f32<T>(*reinterpret_cast<const uint4*>(p), f);
+        a = f32x4{f[0], f[1], f[2], f[3]};
+        b = f32x4{f[4], f[5], f[6], f[7]};
+    }
+}
+
+// MADM_IGEMM_WIDE_EPI=0: the LDS-DMA kernels (igemm_glds_kernel, conv3x3_halo_dma_kernel) keep the plain channel mapping and the
+// per-chunk epilogue stores (A/B runs); read once.
+inline bool igemm_wide_epi() {
+    static const bool on = [] { const char* e = getenv("MADM_IGEMM_WIDE_EPI"); return !(e && atoi(e) == 0); }();
+    return on;
+}
+
+// Permuted mapping (CS = 4): may this LAUNCH move a lane's contiguous span in wide pieces?  Block-uniform, from the launch
+// parameters alone.  A wide piece covers GU chunks under GEGLU (2 * GU outputs: 8 bytes at NI = 2, 16 at NI = 4 in the 16-bit
+// modes, 16 in f32) and two chunks otherwise (16 bytes, 16-bit modes only: an f32 chunk is a 16-byte store already).  It needs
+// the base pointer and the row stride aligned to the piece and N a multiple of its channels, so that no piece straddles N; a
+// launch that fails any of these leaves in the per-chunk pieces of the same span, under the alignment rules of madm_hip.h.
+template <typename T, int NI> struct EpiWide {
+    static constexpr int GU = (sizeof(T) == 2 && NI == 4) ? 4 : 2;
+    static __device__ __forceinline__ bool al(const void* q, unsigned n) { return (reinterpret_cast<uintptr_t>(q) & (n - 1)) == 0; }
+    static __device__ __forceinline__ bool ok(const IgemmP& p) {
+        if (NI % 2 != 0) return false;
+        if (p.epilogue == MADM_EPI_GEGLU)   // (GEGLU + residual takes epilogue_row)
+            return al(p.out, 2 * GU * sizeof(T)) && p.ldo % (2 * GU) == 0 && p.N % (4 * GU) == 0;
+        if (sizeof(T) == 4 || p.out_f32) return false;
+        return al(p.out, 16) && p.ldo % 8 == 0 && p.N % 8 == 0 && (!p.residual || (al(p.residual, 16) && p.ldr % 8 == 0));
+    }
+};
 
 // The MI x NI sub-tiles of one wave: constants, residual, activation for ALL rows first, then all the stores back to
 // back -- no load (and so no vmcnt(0), see epilogue_consts) between two stores; the residual pieces of all rows are in
 // flight together.  mrow[i] = output row of sub-tile row i or -1 (outside the tensor).  Same operation order per element
 // as epilogue_row ((acc + constants) + residual, activation): bit-identical results.  Tiles that straddle images with
 // a time row (img_rows) keep the row-by-row form.  acc returns the stored values (fused statistics).
-template <typename T, int MI, int NI>
+// CS: see epilogue_row.  ``wide`` (CS = 4 only, EpiWide::ok): residual loads and stores in wide pieces, converted and stored
+// row by row (store-issue-bound at short K: half / a quarter of the store instructions for the same bytes).
+template <typename T, int MI, int NI, int CS = 16>
 __device__ __forceinline__ void epilogue_tile(const IgemmP& p, const int (&mrow)[MI], int nb, const f32x4 (&add)[NI],
-                                              bool img_rows, f32x4 (&acc)[MI][NI]) {
+                                              bool img_rows, f32x4 (&acc)[MI][NI], bool wide = false) {
     if ((p.rowvec && img_rows) || (p.epilogue == MADM_EPI_GEGLU && p.residual)) {   // block-uniform, rare
 #pragma unroll
         for (int i = 0; i < MI; ++i)
-            if (mrow[i] >= 0) epilogue_row<T, NI>(p, mrow[i], nb, add, img_rows, acc[i]);
+            if (mrow[i] >= 0) epilogue_row<T, NI, CS>(p, mrow[i], nb, add, img_rows, acc[i]);
         return;
     }
     if (p.epilogue == MADM_EPI_GEGLU) {
@@ -332,13 +382,33 @@ __device__ __forceinline__ void epilogue_tile(const IgemmP& p, const int (&mrow)
                 const f32x4 t = acc[i][j] + add[j];
                 acc[i][j] = f32x4{t[0] * gelu_erf_f(t[1]), t[2] * gelu_erf_f(t[3]), 0.f, 0.f};
             }
+        if constexpr (CS == 4 && NI % 2 == 0) {
+            if (wide) {
+                constexpr int GU = EpiWide<T, NI>::GU;
+#pragma unroll
+                for (int i = 0; i < MI; ++i) {
+                    if (mrow[i] < 0) continue;
+                    T* op = reinterpret_cast<T*>(p.out) + (size_t)mrow[i] * p.ldo + (nb >> 1);
+#pragma unroll
+                    for (int j = 0; j < NI; j += GU) {
+                        if (nb + 4 * j >= p.N) continue;
+                        const f32x4 lo = f32x4{acc[i][j][0], acc[i][j][1], acc[i][j + 1][0], acc[i][j + 1][1]};
+                        if constexpr (GU == 4)
+                            store8<T>(op + 2 * j, lo, f32x4{acc[i][j + 2][0], acc[i][j + 2][1], acc[i][j + 3][0], acc[i][j + 3][1]});
+                        else
+                            store4<T>(op + 2 * j, lo);
+                    }
+                }
+                return;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             if (mrow[i] < 0) continue;
             T* op = reinterpret_cast<T*>(p.out) + (size_t)mrow[i] * p.ldo + (nb >> 1);
 #pragma unroll
             for (int j = 0; j < NI; ++j)
-                if (nb + 16 * j < p.N) store2<T>(op + 8 * j, acc[i][j][0], acc[i][j][1]);
+                if (nb + CS * j < p.N) store2<T>(op + (CS / 2) * j, acc[i][j][0], acc[i][j][1]);
         }
         return;
     }
@@ -350,11 +420,25 @@ __device__ __forceinline__ void epilogue_tile(const IgemmP& p, const int (&mrow)
         // unconditional loads (rows / columns outside the tensor read a valid element instead; their sums are neither
         // stored nor counted): all MI x NI pieces in flight together, one wait
         f32x4 r[MI][NI];
+        bool loaded = false;
+        if constexpr (CS == 4 && NI % 2 == 0) {
+            if (wide) {
 #pragma unroll
-        for (int i = 0; i < MI; ++i) {
-            const T* rp = reinterpret_cast<const T*>(p.residual) + (size_t)(mrow[i] < 0 ? 0 : mrow[i]) * p.ldr;
+                for (int i = 0; i < MI; ++i) {
+                    const T* rp = reinterpret_cast<const T*>(p.residual) + (size_t)(mrow[i] < 0 ? 0 : mrow[i]) * p.ldr;
 #pragma unroll
-            for (int j = 0; j < NI; ++j) r[i][j] = load4<T>(rp + (nb + 16 * j < p.N ? nb + 16 * j : p.N - 4));
+                    for (int j = 0; j < NI; j += 2) load8<T>(rp + (nb + 4 * j < p.N ? nb + 4 * j : p.N - 8), r[i][j], r[i][j + 1]);
+                }
+                loaded = true;
+            }
+        }
+        if (!loaded) {
+#pragma unroll
+            for (int i = 0; i < MI; ++i) {
+                const T* rp = reinterpret_cast<const T*>(p.residual) + (size_t)(mrow[i] < 0 ? 0 : mrow[i]) * p.ldr;
+#pragma unroll
+                for (int j = 0; j < NI; ++j) r[i][j] = load4<T>(rp + (nb + CS * j < p.N ? nb + CS * j : p.N - 4));
+            }
         }
 #pragma unroll
         for (int i = 0; i < MI; ++i)
@@ -370,6 +454,19 @@ __device__ __forceinline__ void epilogue_tile(const IgemmP& p, const int (&mrow)
                 v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
             }
     }
+    if constexpr (CS == 4 && NI % 2 == 0) {
+        if (wide) {   // 16-bit output (EpiWide::ok): one 16-byte store per pair of chunks
+#pragma unroll
+            for (int i = 0; i < MI; ++i) {
+                if (mrow[i] < 0) continue;
+                T* op = reinterpret_cast<T*>(p.out) + (size_t)mrow[i] * p.ldo + nb;
+#pragma unroll
+                for (int j = 0; j < NI; j += 2)
+                    if (nb + 4 * j < p.N) store8<T>(op + 4 * j, acc[i][j], acc[i][j + 1]);
+            }
+            return;
+        }
+    }
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
         if (mrow[i] < 0) continue;
@@ -377,12 +474,12 @@ __device__ __forceinline__ void epilogue_tile(const IgemmP& p, const int (&mrow)
             float* op = reinterpret_cast<float*>(p.out) + (size_t)mrow[i] * p.ldo + nb;
 #pragma unroll
             for (int j = 0; j < NI; ++j)
-                if (nb + 16 * j < p.N) store4<float>(op + 16 * j, acc[i][j]);
+                if (nb + CS * j < p.N) store4<float>(op + CS * j, acc[i][j]);
         } else {
             T* op = reinterpret_cast<T*>(p.out) + (size_t)mrow[i] * p.ldo + nb;
 #pragma unroll
             for (int j = 0; j < NI; ++j)
-                if (nb + 16 * j < p.N) store4<T>(op + 16 * j, acc[i][j]);
+                if (nb + CS * j < p.N) store4<T>(op + CS * j, acc[i][j]);
         }
     }
 }
