@@ -339,8 +339,8 @@ class FeatureExtractorBackbone(nn.Module):
             "backbone_in_size is a multiple of 64 in every shipped config"
         return img
 
-    def checkpoint_forward_features(self, features, input_image_size, ema_forward=False):
-        return self.forward_features(features, input_image_size, ema_forward)
+    def checkpoint_forward_features(self, features, input_image_size, ema_forward=False, tape=None):
+        return self.forward_features(features, input_image_size, ema_forward, tape=tape)
 
     def single_forward(self, img, input_modal='rgb', ema_forward=False, timestep=None, **kwargs):
         input_image_size = img.shape[-2:]
@@ -407,7 +407,9 @@ class AttentionFeatureExtractorBackbone(FeatureExtractorBackbone):
         self._out_feature_strides = {s: 2 ** int(s[1]) for s in out_features}
         self._out_features = list(self._out_feature_strides.keys())
 
-    def forward_features(self, features, input_image_size, ema_forward=False):
+    def forward_features(self, features, input_image_size, ema_forward=False, tape=None):
+        """``tape`` (a list, the training step's): the projections' backward records are appended to it, one
+        (index, output name, feature width, block records) entry per output, for :meth:`backward_features`."""
         self.attention_features = dict()
         features_dict = {}
         for f in features:   # Tok (HIP path) or NCHW tensor
@@ -420,7 +422,6 @@ class AttentionFeatureExtractorBackbone(FeatureExtractorBackbone):
         if self.feature_extractor.ldm_extractor.final_fuse_vae_decoder_feat:
             out_tok['s0'] = features_dict[512]
         projections = self.ema_feature_projections if ema_forward else self.feature_projections
-        tape = getattr(self, "_tape", None)      # set by forward_features_recorded (the training step)
         for idx, name in enumerate(self._out_features):
             res = self.feature_res(name)
             h = features_dict[res]
@@ -441,14 +442,6 @@ class AttentionFeatureExtractorBackbone(FeatureExtractorBackbone):
         """Width of the extractor feature that feeds output ``name``: ``512 // stride`` in the reference
         (feature_extractor.py:383, 512 = backbone_in_size); generalised to the configured backbone_in_size."""
         return self.backbone_in_size[1] // self._out_feature_strides[name]
-
-    def forward_features_recorded(self, features, input_image_size, tape):
-        """:meth:`forward_features` with the projections' backward records appended to ``tape`` (student projections)."""
-        self._tape = tape
-        try:
-            return self.forward_features(features, input_image_size, ema_forward=False)
-        finally:
-            self._tape = None
 
     def backward_features(self, tape, dfeats, no_grad_inputs=()):
         """dfeats: {output name: gradient tokens [M, C_out]} -> ({feature width: gradient tokens of that extractor

@@ -4,8 +4,11 @@ The reference trains through torch autograd (``losses.backward()``, engine/train
 a module is an explicit function over the same channels-last ``Tok`` tensors its forward uses, built from
 ``madm_conv2d_wgrad`` / the forward conv on repacked weights (data gradient) / ``madm_attention_bwd`` /
 ``madm_groupnorm_bwd_*`` / ``madm_layernorm_bwd`` / ``madm_geglu_bwd``.  Activations are RECOMPUTED from the block input
-(the forward keeps nothing but what its caller holds): ``unet_backward`` re-runs the forward keeping only block inputs
-and every block's backward recomputes its interior -- no activation stash beyond ~40 block-boundary tensors.
+(the forward keeps nothing but what its caller holds).  The UNet has ONE forward, ``sd_unet.UNet2DConditionModel.forward``:
+given ``tape=_Tape()`` it also appends every block's input and output to the tape, ``unet_backward_from_state`` walks that
+tape in reverse and every block's backward recomputes its interior -- no activation stash beyond ~40 block-boundary tensors.
+The tape is the caller's and travels by argument (``ldm_rocm.LdmRocm._stage_unet(..., tape=)``), like the ``tape=``
+containers of the projections and the head.
 
 Parameter gradients come back as ``{parameter name: f32 tensor in the nn.Parameter's own shape}``; ``ldm_rocm._UNetTapsFn``
 hands them to torch autograd (``p.grad``), ``train.ExtractorTrainer`` accumulates them into an ``optim.FlatParams`` buffer.
@@ -18,8 +21,6 @@ Levels, each tested against torch autograd (tests/test_ops_gpu.py, tests/test_pa
 Not here: the backward of the HIP projections / DAFormer head, and of the VAE -- its parameters are frozen
 (LdmDiffusers._freeze) and its input images do not require grad, so the reference's autograd never enters it either.
 """
-from types import SimpleNamespace
-
 import torch
 
 from . import ops, packing
@@ -364,12 +365,18 @@ def _block_forward_kv(blk, h, B, L, Lk, kv):
 
 
 class _Tape:
-    """Gradients keyed by the activation tensors of a recorded forward (the tape keeps them alive, so data_ptr() is a
-    unique key); a tensor feeding several consumers accumulates through madm_add."""
+    """What ``sd_unet.UNet2DConditionModel.forward(..., tape=...)`` leaves for :func:`unet_backward_from_state`: the
+    block-boundary ``records`` in forward order, and the call's inputs and time-embedding / K/V intermediates by name.
+    ``g``: gradients keyed by the recorded activation tensors (the tape keeps them alive, so data_ptr() is a unique key);
+    a tensor feeding several consumers accumulates through madm_add.  ``n_enc`` is ``ldm_rocm.LdmRocm._stage_unet``'s: the
+    number of encoder taps in front of the UNet taps in the feature list it returned."""
 
     def __init__(self):
         self.records = []
         self.g = {}
+        self.unet = self.sample = self.ctx = self.Lk = self.cond_emb = None            # the call
+        self.t_emb = self.e1 = self.a1 = self.emb = self.rows = self.kvs = None        # time embedding, time rows, CtxKV views
+        self.h = self.tapped = self.n_enc = None                                       # conv_norm_out's input, the taps
 
     def add(self, t, g):
         cur = self.g.get(t.data_ptr())
@@ -379,81 +386,26 @@ class _Tape:
         return self.g.pop(t.data_ptr(), None)
 
 
-def unet_forward_recorded(unet, sample, timesteps, ctx, Lk, unet_block_indices, cond_emb=None):
-    """``sd_unet.UNet2DConditionModel.forward(sample, timesteps, ctx, Lk, cond_emb, unet_block_indices, 'after')`` run block
-    by block while recording every block's INPUT on a tape (block interiors are not kept).  Returns
-    (sample_out Tok, tapped features list[Tok], state for :func:`unet_backward_from_state`)."""
-    from .sd_unet import CtxKV
-    dtype = sample.t.dtype
-    B = sample.B
-    names = {id(m): n for n, m in unet.named_modules()}
-    tape = _Tape()
-    rec = tape.records
-
-    # ---- recorded forward (mirrors UNet2DConditionModel.forward) ----
-    freqs = ops.timestep_freqs(unet.block_out_channels[0], sample.t.device)
-    t_emb = ops.timestep_embedding(timesteps, freqs, dtype)
-    te = unet.time_embedding
-    e1 = te.linear_1(t_emb)
-    a1 = ops.silu(e1)
-    res = None if cond_emb is None else ops.cast_from_f32(cond_emb.contiguous(), dtype)
-    emb = te.linear_2(a1, residual=res)
-    rows = unet._time_rows(emb)
-    ctxkv = unet._ctx_kv(ctx)
-    kvs = ctxkv.kv if isinstance(ctxkv, CtxKV) else None
-
-    def run_tr(tr, h):
-        out = tr(h, ctxkv, Lk)
-        rec.append(("tr", tr, h, out))
-        return out
-
-    def run_res(r, h, skip=None):
-        out = r(h, rows[id(r)], skip=skip)
-        rec.append(("res", r, h, skip, out))
-        return out
-
-    h = unet.conv_in(sample)
-    rec.append(("conv_in", unet.conv_in, sample, h))
-    skips = [h]
-    for blk in unet.down_blocks:
-        for i, r in enumerate(blk.resnets):
-            h = run_res(r, h)
-            if blk.has_cross_attention:
-                h = run_tr(blk.attentions[i], h)
-            skips.append(h)
-        if blk.downsamplers is not None:
-            for d in blk.downsamplers:
-                x_in = h
-                h = d(h)
-                rec.append(("conv", d.conv, x_in, h, False))
-            skips.append(h)
-    mb = unet.mid_block
-    h = run_res(mb.resnets[0], h)
-    for attn, r in zip(mb.attentions, mb.resnets[1:]):
-        h = run_tr(attn, h)
-        h = run_res(r, h)
-    idx, tapped = 0, []
-    for blk in unet.up_blocks:
-        for i, r in enumerate(blk.resnets):
-            h = run_res(r, h, skip=skips.pop())
-            if blk.has_cross_attention:
-                h = run_tr(blk.attentions[i], h)
-            if idx in unet_block_indices:
-                tapped.append(h)
-            idx += 1
-        if blk.upsamplers is not None:
-            for u in blk.upsamplers:
-                x_in = h
-                h = u(h)
-                rec.append(("conv", u.conv, x_in, h, True))
-    out = unet.conv_out(h, norm=unet.conv_norm_out, stats=False)
-    st = SimpleNamespace(unet=unet, sample=sample, ctx=ctx, Lk=Lk, cond_emb=cond_emb, dtype=dtype, B=B, names=names,
-                         tape=tape, rows=rows, kvs=kvs, emb=emb, e1=e1, a1=a1, t_emb=t_emb, h=h, tapped=tapped)
-    return out, tapped, st
+def wants_base_grads(unet):
+    """False in the reference's LoRA mode: every trainable UNet parameter is a LoRA A / B matrix."""
+    return any(p.requires_grad and ".lora_" not in n for n, p in unet.named_parameters())
 
 
-def unet_backward_from_state(st, dtaps, dsample=None, base_grads=True, grad_cb=None):
-    """Reverse walk over the tape of :func:`unet_forward_recorded` for the gradients ``dtaps`` of the tapped features
+def sample_grad_tokens(unet, dsample, dtype):
+    """NCHW f32 gradient of the UNet's final sample -> channels-last tokens as wide as conv_out's data gradient reads
+    them (its padded output channels, at least one 16-byte chunk)."""
+    cpad = max(unet.conv_out.n_pad, 16 // torch.empty(0, dtype=dtype).element_size())
+    return ops.nchw_to_nhwc(dsample.float().contiguous(), dtype, cpad)
+
+
+def prompt_grad(dctx, shape):
+    """``unet_backward_from_state(...)["ctx"]`` ([B*Lk, padded width] tokens) -> f32 gradient of the prompt embeddings
+    of ``shape`` = (B, Lk, width)."""
+    return ops.rows_to_f32(dctx)[:, :shape[2]].reshape(shape)
+
+
+def unet_backward_from_state(tape, dtaps, dsample=None, base_grads=True, grad_cb=None):
+    """Reverse walk over the tape of a ``unet(..., tape=tape)`` forward for the gradients ``dtaps`` of the tapped features
     ([M_i, C_i] tensors, same order) and, optionally, ``dsample`` of the final sample ([M, n_pad]); every block's
     backward recomputes its interior.
 
@@ -462,12 +414,12 @@ def unet_backward_from_state(st, dtaps, dsample=None, base_grads=True, grad_cb=N
     the norms' affine parameters and the time-row projections come back.  ``grad_cb(name, tensor)``: called for every
     parameter gradient AS SOON AS its block's backward has run (up blocks first, conv_in last, then the batched K/V and
     time-embedding tails) instead of collecting them -- the hook the overlapped gradient all-reduce hangs on."""
-    unet, sample, ctx, Lk, cond_emb, dtype, B, names = st.unet, st.sample, st.ctx, st.Lk, st.cond_emb, st.dtype, st.B, st.names
-    tape, rows, kvs, emb, e1, a1, t_emb, h, tapped = st.tape, st.rows, st.kvs, st.emb, st.e1, st.a1, st.t_emb, st.h, st.tapped
-    rec = tape.records
+    unet, sample, ctx, Lk, rows, kvs, emb, h = tape.unet, tape.sample, tape.ctx, tape.Lk, tape.rows, tape.kvs, tape.emb, tape.h
+    dtype, B = sample.t.dtype, sample.B
+    names = {id(m): n for n, m in unet.named_modules()}
     te = unet.time_embedding
-    assert len(tapped) == len(dtaps)
-    for tk, g in zip(tapped, dtaps):
+    assert len(tape.tapped) == len(dtaps)
+    for tk, g in zip(tape.tapped, dtaps):
         tape.add(tk.t, g)
 
     class _Grads(dict):
@@ -499,47 +451,30 @@ def unet_backward_from_state(st, dtaps, dsample=None, base_grads=True, grad_cb=N
         tape.add(h.t, dh)
 
     # ---- reverse walk ----
-    for r_ in reversed(rec):
-        kind = r_[0]
+    for kind, mod, x, *more, out in reversed(tape.records):
+        dout = tape.pop(out.t)
+        if dout is None:   # nothing behind this block reaches a tap (or the sample)
+            continue
+        skip, dkvs = None, ()
         if kind == "res":
-            _, mod, x, skip, out = r_
-            dout = tape.pop(out.t)
-            if dout is None:
-                continue
-            dx, dskip, dtr, g = resnet_block_backward(mod, x, dout, temb_row=rows[id(mod)], skip=skip,
-                                                      base_grads=base_grads)
-            put(names[id(mod)], g)
-            drow[id(mod)] = dtr
-            tape.add(x.t, dx.t)
-            if skip is not None:
-                tape.add(skip.t, dskip.t)
+            skip, = more
+            dx, dskip, drow[id(mod)], g = resnet_block_backward(mod, x, dout, temb_row=rows[id(mod)], skip=skip,
+                                                                base_grads=base_grads)
+            dx = dx.t
         elif kind == "tr":
-            _, mod, x, out = r_
-            dout = tape.pop(out.t)
-            if dout is None:
-                continue
             dx, dkvs, g = transformer2d_backward(mod, x, dout, ctx, Lk, kvs=kvs, base_grads=base_grads)
-            put(names[id(mod)], g)
-            tape.add(x.t, dx)
-            for blk, dkv in zip(mod.transformer_blocks, dkvs):
-                if kvs is not None:
-                    dkv_of[id(blk.attn2)] = dkv
-                else:
-                    dctx = dkv if dctx is None else ops.add(dctx, dkv)
-        elif kind == "conv":
-            _, conv, x, out, ups = r_
-            dout = tape.pop(out.t)
-            if dout is None:
-                continue
-            dx, g = conv2d_backward(conv, x, dout, upsample=ups, need_dw=base_grads)
-            put(names[id(conv)], g)
-            tape.add(x.t, dx)
-        elif kind == "conv_in":
-            _, conv, x, out = r_
-            dout = tape.pop(out.t)
-            dx, g = conv2d_backward(conv, x, dout, need_dw=base_grads)
-            put("conv_in", g)
-            tape.add(x.t, dx)
+        else:   # "conv": conv_in and the down / up sampler convs
+            upsampled, = more
+            dx, g = conv2d_backward(mod, x, dout, upsample=upsampled, need_dw=base_grads)
+        put(names[id(mod)], g)   # (grad_cb's launches come before the accumulations below)
+        tape.add(x.t, dx)
+        if skip is not None:
+            tape.add(skip.t, dskip.t)
+        for blk, dkv in zip(getattr(mod, "transformer_blocks", ()), dkvs):
+            if kvs is not None:
+                dkv_of[id(blk.attn2)] = dkv
+            else:
+                dctx = dkv if dctx is None else ops.add(dctx, dkv)
     dsample_in = tape.pop(sample.t)
 
     # ---- batched K/V projection of the cross-attention layers (no LoRA on to_k / to_v) ----
@@ -585,18 +520,19 @@ def unet_backward_from_state(st, dtaps, dsample=None, base_grads=True, grad_cb=N
         off += n
     ds = ops.conv2d_dgrad(drows_c, ops.pack_dgrad_weights(Wp, 1), 1, B, 1, C=Wp.shape[1])
     demb = ops.silu_backward(emb, _cols(ds, emb.shape[1]))
-    da1, g = linear_backward(te.linear_2, a1, demb, need_dw=base_grads)
+    da1, g = linear_backward(te.linear_2, tape.a1, demb, need_dw=base_grads)
     put("time_embedding.linear_2", g)
     if base_grads:
-        de1 = ops.silu_backward(e1, _cols(da1, e1.shape[1]))
-        _, g = linear_backward(te.linear_1, t_emb, de1, need_dx=False)
+        de1 = ops.silu_backward(tape.e1, _cols(da1, tape.e1.shape[1]))
+        _, g = linear_backward(te.linear_1, tape.t_emb, de1, need_dx=False)
         put("time_embedding.linear_1", g)
-    return {"sample": dsample_in, "ctx": dctx, "cond_emb": ops.rows_to_f32(demb) if cond_emb is not None else None,
+    return {"sample": dsample_in, "ctx": dctx, "cond_emb": ops.rows_to_f32(demb) if tape.cond_emb is not None else None,
             "grads": grads}
 
 
 def unet_backward(unet, sample, timesteps, ctx, Lk, dtaps, unet_block_indices, cond_emb=None, dsample=None,
                   base_grads=True):
-    """:func:`unet_forward_recorded` + :func:`unet_backward_from_state` in one call (see there)."""
-    _, _, st = unet_forward_recorded(unet, sample, timesteps, ctx, Lk, unet_block_indices, cond_emb=cond_emb)
-    return unet_backward_from_state(st, dtaps, dsample=dsample, base_grads=base_grads)
+    """The UNet forward on a fresh tape + :func:`unet_backward_from_state` in one call (see there)."""
+    tape = _Tape()
+    unet(sample, timesteps, ctx, Lk, cond_emb=cond_emb, unet_block_indices=unet_block_indices, tape=tape)
+    return unet_backward_from_state(tape, dtaps, dsample=dsample, base_grads=base_grads)

@@ -208,10 +208,10 @@ def _unet_inputs(x, timestep, encoder_hidden_states, res_time_embedding):
 
 
 def _unet_tokens(unet, x, timestep, encoder_hidden_states, res_time_embedding, unet_block_indices,
-                 unet_block_indices_type):
+                 unet_block_indices_type, tape=None):
     timestep, ctx, Lk, cond = _unet_inputs(x, timestep, encoder_hidden_states, res_time_embedding)
     return unet(x, timestep, ctx, Lk, cond_emb=cond, unet_block_indices=tuple(unet_block_indices),
-                unet_block_indices_type=unet_block_indices_type)
+                unet_block_indices_type=unet_block_indices_type, tape=tape)
 
 
 class LdmRocm(nn.Module):
@@ -388,16 +388,19 @@ class LdmRocm(nn.Module):
         # two stages with a narrow hand-over (the noisy latents), so that a serving loop can capture / schedule them
         # separately: madm_amd/pipeline.py runs the encoder stage of every batch on one stream and the UNet stages of
         # consecutive batches side by side on three
-        want_grad = torch.is_grad_enabled() and self._wants_grad(batched_inputs, kwargs)
+        tape = None
+        if torch.is_grad_enabled() and self._wants_grad(batched_inputs, kwargs):
+            from . import backward as bw
+            tape = bw._Tape()
         with torch.no_grad(), ops.sync_profile():       # (one batch in flight: the lone-launch rows; a no-op inside the graph runners)
             st = self._stage_encode(batched_inputs)
             hook = self.__dict__.get("stage_hook")
             if hook is not None:          # pipeline.StagedInference: the stage boundary of a whole-model forward (capture / stream switch)
                 hook("encoded")
-            out = self._stage_unet(st, batched_inputs, _keep_for_grad=want_grad, **kwargs)
-        if not want_grad:
+            out = self._stage_unet(st, batched_inputs, tape=tape, **kwargs)
+        if tape is None:
             return out
-        return self._attach_unet_grad(out, batched_inputs, kwargs)
+        return self._attach_unet_grad(out, batched_inputs, tape)
 
     # ---- training: the UNet stage as one autograd node ("differentiable w.r.t. its requires_grad
     #      params through standard autograd") ----
@@ -410,25 +413,22 @@ class LdmRocm(nn.Module):
         return any(x is not None and torch.is_tensor(x) and x.requires_grad for x in t) or \
             any(p.requires_grad for p in self.unet.parameters())
 
-    def _attach_unet_grad(self, out, batched_inputs, kwargs):
+    def _attach_unet_grad(self, out, batched_inputs, tape):
         """Re-issues the UNet taps (and the final sample, when it was asked for) as outputs of ``_UNetTapsFn``: the
-        values are the ones the forward just computed, the node's backward is ``backward.unet_backward``."""
-        keep = self._grad_keep
-        self._grad_keep = None
+        values are the ones the forward just computed, the node's backward is ``backward.unet_backward_from_state`` over
+        ``tape``, which ``_stage_unet`` had the UNet forward fill."""
         extra = None
         if isinstance(out, tuple):
             feats, extra = out
         else:
             feats = out
-        n_enc = keep["n_enc"]
-        n_taps = len(keep["taps"])
+        n_enc = tape.n_enc
+        n_taps = len(tape.tapped)
         with_sample = isinstance(extra, dict)
         named = [(n, p) for n, p in self.unet.named_parameters() if p.requires_grad]
-        keep["param_names"] = [n for n, _ in named]
-        keep["with_sample"] = with_sample
         values = list(feats[n_enc:n_enc + n_taps]) + ([extra['before_vae.decoder']] if with_sample else [])
-        outs = _UNetTapsFn.apply(keep, batched_inputs['cond_inputs'], batched_inputs['cond_emb'], len(values), *values,
-                                 *[p for _, p in named])
+        outs = _UNetTapsFn.apply(tape, [n for n, _ in named], batched_inputs['cond_inputs'], batched_inputs['cond_emb'],
+                                 len(values), *values, *[p for _, p in named])
         feats = list(feats)
         feats[n_enc:n_enc + n_taps] = outs[:n_taps]
         if with_sample:
@@ -472,8 +472,10 @@ class LdmRocm(nn.Module):
         return {"B": B, "h": h, "w": w, "noisy": noisy, "latents": latents, "timesteps": timesteps, "enc_taps": enc_taps,
                 "minmax": minmax}
 
-    def _stage_unet(self, st, batched_inputs, **kwargs):
-        """diffusion_unet on the noisy latents + the feature hand-over (ldm_diffusers.py:165-217)."""
+    def _stage_unet(self, st, batched_inputs, tape=None, **kwargs):
+        """diffusion_unet on the noisy latents + the feature hand-over (ldm_diffusers.py:165-217).  ``tape`` (training: a
+        ``backward._Tape`` of the caller's): the UNet forward records itself on it for ``backward.unet_backward_from_state``,
+        and ``tape.n_enc`` says how many encoder taps stand in front of the UNet taps in the returned list."""
         dtype = self.compute_dtype
         B, h, w = st["B"], st["h"], st["w"]
         noisy, latents, timesteps, enc_taps, minmax = st["noisy"], st["latents"], st["timesteps"], st["enc_taps"], st["minmax"]
@@ -484,20 +486,8 @@ class LdmRocm(nn.Module):
             forward_unet = self.ema_unet
         else:
             forward_unet = self.unet
-        if kwargs.pop("_keep_for_grad", False):
-            # training: the same forward, run block by block with the block inputs kept for backward.unet_backward_from_state
-            if self.unet_block_indices_type != "after":
-                raise NotImplementedError("autograd through 'in'-type taps")
-            from . import backward as bw
-            x_tok = Tok(noisy, B, h, w)
-            ts_, ctx_, Lk_, cond_ = _unet_inputs(x_tok, timesteps, text_prompt, res_time_embedding)
-            sample, unet_taps, state = bw.unet_forward_recorded(forward_unet, x_tok, ts_, ctx_, Lk_,
-                                                                tuple(self.unet_block_indices), cond_emb=cond_)
-            self._grad_keep = {"unet": forward_unet, "state": state, "B": B, "taps": [t_.C for t_ in unet_taps],
-                               "n_enc": len(enc_taps), "dtype": dtype}
-        else:
-            sample, unet_taps = _unet_tokens(forward_unet, Tok(noisy, B, h, w), timesteps, text_prompt,
-                                             res_time_embedding, self.unet_block_indices, self.unet_block_indices_type)
+        sample, unet_taps = _unet_tokens(forward_unet, Tok(noisy, B, h, w), timesteps, text_prompt, res_time_embedding,
+                                         self.unet_block_indices, self.unet_block_indices_type, tape=tape)
 
         hook = self.__dict__.get("stage_hook")
         if hook is not None:              # the UNet is done: what follows (VAE decoder branch, projections, head) is the third stage
@@ -519,8 +509,8 @@ class LdmRocm(nn.Module):
             # taps of the decoder run on the (scaled) latents, not on the UNet output (:204-205)
             lat_tok = Tok(ops.nchw_to_nhwc(latents, dtype, ops.k_tile(dtype)), B, h, w)
             _, dec_tok = self.vae.decode(lat_tok, tuple(self.decoder_block_indices), output_final=False)
-        if getattr(self, "_grad_keep", None) is not None:
-            self._grad_keep["n_enc"] = len(enc_tok)
+        if tape is not None:
+            tape.n_enc = len(enc_tok)
         if minmax is not None and self.check_input_range and not torch.cuda.is_current_stream_capturing():
             if self.deferred_range_probes is not None:
                 # a caller that synchronises later anyway (train.MadmTrainer at the end of its step) collects the probes and
@@ -555,12 +545,13 @@ class LdmRocm(nn.Module):
 
 class _UNetTapsFn(torch.autograd.Function):
     """The UNet stage of LdmRocm as ONE autograd node: forward hands back the tap tensors the (no-grad) HIP forward
-    already produced; backward runs ``backward.unet_backward`` (block interiors recomputed) and returns the gradients of
+    already produced; backward runs ``backward.unet_backward_from_state`` over the tape that forward filled (block
+    interiors recomputed) and returns the gradients of
     the prompt tokens, the time-embedding residual and every trainable UNet parameter."""
 
     @staticmethod
-    def forward(ctx, keep, cond_inputs, cond_emb, n_values, *rest):
-        ctx.keep = keep
+    def forward(ctx, tape, param_names, cond_inputs, cond_emb, n_values, *rest):
+        ctx.tape, ctx.param_names = tape, param_names
         ctx.cond_shape = None if cond_emb is None else tuple(cond_emb.shape)
         ctx.n_values = n_values
         ctx.save_for_backward(cond_inputs, *([] if cond_emb is None else [cond_emb]))
@@ -574,26 +565,22 @@ class _UNetTapsFn(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, *gouts):
         from . import backward as bw
-        k = ctx.keep
-        unet, dtype, B = k["unet"], k["dtype"], k["B"]
+        tape, names = ctx.tape, ctx.param_names
+        ctx.tape = None            # one backward per forward: the activations go with it
+        unet, dtype = tape.unet, tape.sample.t.dtype
         saved = ctx.saved_tensors
         cond_inputs = saved[0]
         cond_emb = saved[1] if len(saved) > 1 else None
-        n_taps = len(k["taps"])
-
-        def tokens(g, cpad=None):   # NCHW f32 gradient -> channels-last tokens of the compute dtype
-            return ops.nchw_to_nhwc(g.float().contiguous(), dtype, cpad if cpad is not None else g.shape[1])
-
-        dtaps = [tokens(gouts[i]) for i in range(n_taps)]   # autograd materialises zeros for unused outputs
+        n_taps = len(tape.tapped)
+        # NCHW f32 gradients -> channels-last tokens of the compute dtype (autograd materialises zeros for unused outputs)
+        dtaps = [ops.nchw_to_nhwc(g.float().contiguous(), dtype, g.shape[1]) for g in gouts[:n_taps]]
         dsample = None
-        if k["with_sample"] and gouts[n_taps] is not None:
-            dsample = tokens(gouts[n_taps], cpad=max(unet.conv_out.n_pad, 16 // torch.empty(0, dtype=dtype).element_size()))
-        names = k["param_names"]
-        base = any(".lora_" not in n for n in names)
-        res = bw.unet_backward_from_state(k.pop("state"), dtaps, dsample=dsample, base_grads=base)
+        if ctx.n_values > n_taps and gouts[n_taps] is not None:
+            dsample = bw.sample_grad_tokens(unet, gouts[n_taps], dtype)
+        res = bw.unet_backward_from_state(tape, dtaps, dsample=dsample, base_grads=bw.wants_base_grads(unet))
         g_ctx = None
         if cond_inputs.requires_grad:
-            g_ctx = ops.rows_to_f32(res["ctx"])[:, :cond_inputs.shape[2]].reshape(cond_inputs.shape).to(cond_inputs.dtype)
+            g_ctx = bw.prompt_grad(res["ctx"], cond_inputs.shape).to(cond_inputs.dtype)
         g_cond = None
         if cond_emb is not None and cond_emb.requires_grad:
             g_cond = res["cond_emb"].reshape(ctx.cond_shape).to(cond_emb.dtype)
@@ -602,7 +589,7 @@ class _UNetTapsFn(torch.autograd.Function):
         for n in names:
             g = res["grads"].get(n)
             g_params.append(None if g is None else g.reshape(params[n].shape).to(params[n].dtype))
-        return (None, g_ctx, g_cond, None) + (None,) * ctx.n_values + tuple(g_params)
+        return (None, None, g_ctx, g_cond, None) + (None,) * ctx.n_values + tuple(g_params)
 
 
 weights_loader = weights

@@ -10,7 +10,8 @@ One training call = EMA update of the teacher (:184-185), source pass ('default'
 (:261-279), target pass on the mixed image (:284-302), teacher pass under no_grad with the EMA projections / head /
 prompt (:308-337), pseudo labels + label / weight mixing (:339-392), the colour-label latents of the VAE-decoder losses
 (:253-254, 394-397) and ``CmdiseCriterion`` (:441-492).  Every tensor op runs on libmadm_hip kernels: the two gradient
-passes are recorded (block-boundary tape of the UNet, raw conv outputs of projections / head) and the losses come back as
+passes are recorded on tapes that ``_student_pass`` owns and passes down as ``tape=`` arguments (block-boundary tape of the
+UNet's one forward, raw conv outputs of projections / head) and the losses come back as
 the outputs of ONE autograd node (``_TrainStepFn``) whose backward walks those records with the explicit gradient kernels
 (backward.py, head.py, backbone.py, criterion.py), weighting each loss by the upstream gradient it receives.
 
@@ -201,14 +202,12 @@ class MTMADISE(MadmInference):
             cond_inputs, cond_emb = project(gen.uncond_inputs, None, repeat=B)
             batched = dict(img=img, cond_inputs=cond_inputs, cond_emb=cond_emb)
             st = ldm._stage_encode(batched)
-            feats, extra = ldm._stage_unet(st, batched, _keep_for_grad=True, _return_tokens=True,
-                                           return_unet_final_output=True)
-            keep = ldm._grad_keep
-            ldm._grad_keep = None
+            unet_tape = bw._Tape()
+            feats, extra = ldm._stage_unet(st, batched, tape=unet_tape, _return_tokens=True, return_unet_final_output=True)
             proj_tape, head_tape, logits = None, None, None
             if head:
                 proj_tape = []
-                fd = bb.forward_features_recorded(feats, img.shape[-2:], proj_tape)
+                fd = bb.forward_features(feats, img.shape[-2:], tape=proj_tape)
                 hd = self.sem_seg_head
                 head_tape = {}
                 toks = [fd['output_features'].tok[k] for k in hd.in_keys]
@@ -216,7 +215,7 @@ class MTMADISE(MadmInference):
         no_grad_w = ()
         if ldm.vae_decoder_loss and not ldm.final_fuse_vae_decoder_feat:
             no_grad_w = (feats[0].W,)          # the decoder image is ``.detach()``ed (ldm_diffusers.py:196-201)
-        rec = dict(keep=keep, proj_tape=proj_tape, head_tape=head_tape, project=project, B=B, no_grad_w=no_grad_w,
+        rec = dict(unet_tape=unet_tape, proj_tape=proj_tape, head_tape=head_tape, project=project, B=B, no_grad_w=no_grad_w,
                    adapter=self.active_lora_adapter())     # the backward recomputes the fused LoRA operands: same adapter
         return logits, extra, rec
 
@@ -539,11 +538,9 @@ class MTMADISE(MadmInference):
         projections, UNet up -> mid -> down -> conv_in, batched K/V and time-embedding tails, prompt / time gates)."""
         bb = self.backbone
         gen = bb.feature_extractor
-        ldm = gen.ldm_extractor
         self.set_lora_adapter(rec["adapter"])
-        keep = rec["keep"]
-        state = keep["state"]
-        unet, dtype = keep["unet"], keep["dtype"]
+        tape = rec["unet_tape"]
+        unet = tape.unet
         dins = {}
         if dlogits is not None:
             head = self.sem_seg_head
@@ -556,28 +553,27 @@ class MTMADISE(MadmInference):
             for k_, v in pg.items():
                 add(bp[k_], v)
         dtaps = []
-        for tk in state.tapped:
+        for tk in tape.tapped:
             d = dins.get(tk.W)
             if d is None:
                 d = torch.zeros_like(tk.t)
             dtaps.append(d if d.shape[1] == tk.C else d[:, :tk.C].contiguous())
         ds = None
         if dsample is not None:
-            ds = ops.nchw_to_nhwc(dsample.float().contiguous(), dtype, max(unet.conv_out.n_pad, 16 // dsample.new_empty(0, dtype=dtype).element_size()))
+            ds = bw.sample_grad_tokens(unet, dsample, tape.sample.t.dtype)
         up = dict(unet.named_parameters())
-        base = any(p.requires_grad and ".lora_" not in n for n, p in up.items())
 
         def unet_grad(k_, v):
             p = up.get(k_)
             if p is not None and p.requires_grad:
                 add(p, v)
 
-        res = bw.unet_backward_from_state(state, dtaps, dsample=ds, base_grads=base, grad_cb=unet_grad)
+        res = bw.unet_backward_from_state(tape, dtaps, dsample=ds, base_grads=bw.wants_base_grads(unet),
+                                          grad_cb=unet_grad)
         # prompt / time conditioning
         project = rec["project"]
         if any(p.requires_grad for p in project.parameters()):
-            B = rec["B"]
-            dctx = ops.rows_to_f32(res["ctx"])[:, :gen.uncond_inputs.shape[2]].reshape(B, -1, gen.uncond_inputs.shape[2])
+            dctx = bw.prompt_grad(res["ctx"], (rec["B"], -1, gen.uncond_inputs.shape[2]))
             pg = project.backward(gen.uncond_inputs, dctx.contiguous(), res["cond_emb"])
             pp = dict(project.named_parameters())
             for k_, v in pg.items():
@@ -612,7 +608,7 @@ class _TrainStepFn(torch.autograd.Function):
         early = set()
         sink = getattr(model, "grad_sink", None)     # train.MadmTrainer: gradients go straight into its flat buffer and
         passes = []                                  # finished spans are all-reduced while the backward still runs
-        dtype = st["rec_s"]["keep"]["dtype"]
+        dtype = st["rec_s"]["unet_tape"].sample.t.dtype
         for rec, ce_name, dec_name in ((st["rec_s"], 'source_loss', 'vae_decoder_source_loss'),
                                        (st["rec_t"], 'target_loss', 'vae_decoder_target_loss'),
                                        (st["rec_m"], 'masked_prompt_consistency_loss', 'mic_vae_decoder_loss')):

@@ -445,8 +445,12 @@ class TimestepEmbedding(nn.Module):
         self.act = Identity()
         self.linear_2 = Linear(time_embed_dim, time_embed_dim)
 
-    def forward(self, t_emb, residual=None):
-        return self.linear_2(ops.silu(self.linear_1(t_emb)), residual=residual)
+    def forward(self, t_emb, residual=None, tape=None):
+        e1 = self.linear_1(t_emb)
+        a1 = ops.silu(e1)
+        if tape is not None:   # linear_2's and linear_1's backward start from these
+            tape.e1, tape.a1 = e1, a1
+        return self.linear_2(a1, residual=residual)
 
 
 class UNet2DConditionModel(nn.Module):
@@ -586,11 +590,25 @@ class UNet2DConditionModel(nn.Module):
             off += n
         return out
 
-    def forward(self, sample, timesteps, ctx, Lk, cond_emb=None, unet_block_indices=(), unet_block_indices_type="after"):
+    def forward(self, sample, timesteps, ctx, Lk, cond_emb=None, unet_block_indices=(), unet_block_indices_type="after",
+                tape=None):
         """sample: Tok (latents, channels padded to the K-tile); timesteps: int64 [B];
         ctx: [B*Lk, 768] tokens; cond_emb: f32 [B, 1280] or None ("emb += res_time_embedding").
         Returns (sample Tok [.., 4], taps list[Tok]) with the reference's tap semantics
-        (ldm_diffusers.py:372-375,389-392,411-414,442-445)."""
+        (ldm_diffusers.py:372-375,389-392,411-414,442-445).
+
+        ``tape`` (a ``backward._Tape``, the training step's): the same launches, and every block's input and output are
+        appended to ``tape.records`` as ("res", resnet, x, skip, out) / ("tr", transformer, x, out) /
+        ("conv", conv, x, upsampled, out) -- block interiors are not kept -- plus what the tails of
+        ``backward.unet_backward_from_state`` start from, in the tape's named fields."""
+        if tape is not None and unet_block_indices_type != "after":
+            raise NotImplementedError("backward through 'in'-type taps")
+
+        def kept(*record):   # a block boundary: (kind, module, input, ..., output); hands the output on
+            if tape is not None:
+                tape.records.append(record)
+            return record[-1]
+
         dtype = sample.t.dtype
         freqs = self.__dict__.get("_freqs")
         if freqs is None or freqs.device != sample.t.device:
@@ -600,28 +618,28 @@ class UNet2DConditionModel(nn.Module):
         # emb = time_embedding(t_emb); emb += res_time_embedding (ldm_diffusers.py:505-509): the add is
         # the residual input of linear_2's epilogue
         res = None if cond_emb is None else ops.cast_from_f32(cond_emb.contiguous(), dtype)
-        emb = self.time_embedding(t_emb, residual=res)
+        emb = self.time_embedding(t_emb, residual=res, tape=tape)
         rows = self._time_rows(emb)
-        ctx = self._ctx_kv(ctx)
+        prompt, ctx = ctx, self._ctx_kv(ctx)
 
-        h = self.conv_in(sample)
+        h = kept("conv", self.conv_in, sample, False, self.conv_in(sample))
         skips = [h]
         for blk in self.down_blocks:
             for i, resnet in enumerate(blk.resnets):
-                h = resnet(h, rows[id(resnet)])
+                h = kept("res", resnet, h, None, resnet(h, rows[id(resnet)]))
                 if blk.has_cross_attention:
-                    h = blk.attentions[i](h, ctx, Lk)
+                    h = kept("tr", blk.attentions[i], h, blk.attentions[i](h, ctx, Lk))
                 skips.append(h)
             if blk.downsamplers is not None:
                 for d in blk.downsamplers:
-                    h = d(h)
+                    h = kept("conv", d.conv, h, False, d(h))
                 skips.append(h)
 
         mb = self.mid_block
-        h = mb.resnets[0](h, rows[id(mb.resnets[0])])
+        h = kept("res", mb.resnets[0], h, None, mb.resnets[0](h, rows[id(mb.resnets[0])]))
         for attn, resnet in zip(mb.attentions, mb.resnets[1:]):
-            h = attn(h, ctx, Lk)
-            h = resnet(h, rows[id(resnet)])
+            h = kept("tr", attn, h, attn(h, ctx, Lk))
+            h = kept("res", resnet, h, None, resnet(h, rows[id(resnet)]))
 
         taps, idx = [], 0
         for blk in self.up_blocks:
@@ -631,15 +649,19 @@ class UNet2DConditionModel(nn.Module):
                     if idx in unet_block_indices:
                         taps.append((h, skip))  # post-concat tap: two sources, joined at hand-over
                     idx += 1
-                h = resnet(h, rows[id(resnet)], skip=skip)
+                h = kept("res", resnet, h, skip, resnet(h, rows[id(resnet)], skip=skip))
                 if blk.has_cross_attention:
-                    h = blk.attentions[i](h, ctx, Lk)
+                    h = kept("tr", blk.attentions[i], h, blk.attentions[i](h, ctx, Lk))
                 if unet_block_indices_type == "after":
                     if idx in unet_block_indices:
                         taps.append(h)
                     idx += 1
             if blk.upsamplers is not None:
                 for u in blk.upsamplers:
-                    h = u(h)
+                    h = kept("conv", u.conv, h, True, u(h))
         assert len(taps) == len(unet_block_indices)
+        if tape is not None:
+            tape.unet, tape.sample, tape.ctx, tape.Lk, tape.cond_emb = self, sample, prompt, Lk, cond_emb
+            tape.rows, tape.kvs = rows, ctx.kv if isinstance(ctx, CtxKV) else None
+            tape.t_emb, tape.emb, tape.h, tape.tapped = t_emb, emb, h, taps
         return self.conv_out(h, norm=self.conv_norm_out, stats=False), taps

@@ -34,7 +34,7 @@ class MadmTrainer:
         assert table, "nothing to train"
         # flat-buffer order = the order in which the explicit backward FINISHES gradients, reversed: parameters whose
         # gradient only exists at the very end of the backward (prompt / time gates, the time-embedding MLP and the
-        # stacked time_emb_proj / batched cross-attention K/V projections, backward.unet_backward_from_state's tails) go
+        # stacked time_emb_proj / batched cross-attention K/V projections: the tails of backward.unet_backward_from_state) go
         # first, everything else follows in registration order (conv_in ... up blocks, projections, head) -- the backward
         # walks that part back to front, so finished gradients always form a growing TAIL of the buffer
         names = {id(p): n for n, p in model.named_parameters()}

@@ -361,6 +361,29 @@ def test_helper_functions_match_reference_signatures(extractor):
 _UNET_BWD_CACHE = {}
 
 
+def _unet_backward_inputs(lora):
+    """Once per LoRA flag: the HIP-side UNet at full width with the synthetic weights, and its inputs on an 8x8 latent
+    (the smallest map on which every down / up sampler and the 1x1 mid block still run).  ``g``: the generator behind
+    the inputs, for :func:`_unet_backward_reference` to go on drawing from."""
+    if ("inputs", lora) in _UNET_BWD_CACHE:
+        return _UNET_BWD_CACHE["inputs", lora]
+    from madm_amd import weights
+    from madm_amd.sd_unet import UNet2DConditionModel
+    B, hw, Lk, taps = 2, 8, 77, (5, 8, 11)
+    unet = UNet2DConditionModel()
+    weights.synth_init_(unet, 0, "unet.")
+    if lora:
+        add_lora(unet, _LoraConfig)
+    g = torch.Generator().manual_seed(77)
+    sample = torch.randn((B, 4, hw, hw), generator=g).requires_grad_(True)
+    ctx = (0.5 * torch.randn((B, Lk, 768), generator=g)).requires_grad_(True)
+    cond = (0.02 * torch.randn((B, 1280), generator=g)).requires_grad_(True)
+    ts = torch.full((B,), 60, dtype=torch.int64)
+    _UNET_BWD_CACHE["inputs", lora] = dict(unet=unet.cuda(), sample=sample, ctx=ctx, cond=cond, ts=ts, g=g,
+                                           B=B, hw=hw, Lk=Lk, taps=taps)
+    return _UNET_BWD_CACHE["inputs", lora]
+
+
 def _unet_backward_reference(lora):
     """CPU oracle + torch autograd, once per LoRA flag (about 20 s): inputs, loss gradients, reference gradients, and
     the HIP-side UNet holding the same synthetic weights."""
@@ -368,28 +391,19 @@ def _unet_backward_reference(lora):
         return _UNET_BWD_CACHE[lora]
     from oracle import sd_modules, ldm_path
     from madm_amd import weights
-    from madm_amd.sd_unet import UNet2DConditionModel
-    B, hw, Lk, taps = 2, 8, 77, (5, 8, 11)
+    r = _unet_backward_inputs(lora)
     ref_unet = sd_modules.UNet2DConditionModel()
-    unet = UNet2DConditionModel()
     weights.synth_init_(ref_unet, 0, "unet.")
-    weights.synth_init_(unet, 0, "unet.")
     if lora:
         add_lora(ref_unet, sd_modules.LoraConfig)
-        add_lora(unet, _LoraConfig)
-    g = torch.Generator().manual_seed(77)
-    sample = torch.randn((B, 4, hw, hw), generator=g).requires_grad_(True)
-    ctx = (0.5 * torch.randn((B, Lk, 768), generator=g)).requires_grad_(True)
-    cond = (0.02 * torch.randn((B, 1280), generator=g)).requires_grad_(True)
-    ts = torch.full((B,), 60, dtype=torch.int64)
-    out, feats = ldm_path.diffusion_unet(ref_unet, sample, ts, ctx, cond, taps, "after")
+    g = r["g"]
+    out, feats = ldm_path.diffusion_unet(ref_unet, r["sample"], r["ts"], r["ctx"], r["cond"], r["taps"], "after")
     gs = [torch.randn(f.shape, generator=g) for f in feats]
     gout = torch.randn(out.sample.shape, generator=g)
     loss = sum((f * g_).sum() for f, g_ in zip(feats, gs)) + (out.sample * gout).sum()
     loss.backward()
     want = {n: p.grad for n, p in ref_unet.named_parameters() if p.grad is not None}
-    _UNET_BWD_CACHE[lora] = dict(unet=unet.cuda(), sample=sample, ctx=ctx, cond=cond, ts=ts, gs=gs, gout=gout, want=want,
-                                 B=B, hw=hw, Lk=Lk, taps=taps)
+    _UNET_BWD_CACHE[lora] = dict(r, gs=gs, gout=gout, want=want)
     return _UNET_BWD_CACHE[lora]
 
 
@@ -438,6 +452,105 @@ def test_unet_backward_equals_oracle_autograd(cuda, dtype, lora):
     ranked = sorted(results, key=lambda t: -float(t[1].split("l2 ")[1]))
     print(dtype, "lora" if lora else "plain", len(results), "tensors; worst three:", [m for _, m in ranked[:3]])
     assert not bad, bad[:8]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_unet_taped_forward_is_the_forward(cuda, extractor, dtype):
+    """The training step records the UNet by handing ``UNet2DConditionModel.forward`` a tape: there is one walk.  On the
+    full-width UNet (LoRA active, 8x8 latent) the taped call returns bit-identical values and issues the identical
+    launches as the plain call (which is itself bit-repeatable: the fused statistics are f64 sums of f32 partials), and
+    as the forward half of backward.unet_backward; the tape holds every module once, in forward order; 'in'-type taps
+    refuse a tape; and a taped call leaves no attribute behind on the UNet, the extractor or the backbone."""
+    from madm_amd import backward, ops
+    from madm_amd.backbone import BasePromptTimeGenerator, AttentionFeatureExtractorBackbone
+    from madm_amd.nn import Tok
+    from madm_amd.sd_unet import Transformer2DModel
+    from util import to_tokens
+    r = _unet_backward_inputs(True)
+    unet, B, hw, Lk, taps = r["unet"], r["B"], r["hw"], r["Lk"], r["taps"]
+    x = Tok(to_tokens(r["sample"].detach(), dtype, ops.k_tile(dtype)), B, hw, hw)
+    ctx = r["ctx"].detach().reshape(B * Lk, 768).to(dtype).cuda()
+    ts, cond = r["ts"].cuda(), r["cond"].detach().cuda()
+
+    def logged(fn):
+        saved, ops.TILE_LOG = ops.TILE_LOG, []
+        try:
+            out = fn()
+            torch.cuda.synchronize()
+            return out, [e[:3] for e in ops.TILE_LOG]     # (description, tile, split-K)
+        finally:
+            ops.TILE_LOG = saved
+
+    def values(out):
+        return [out[0].t] + [t.t for t in out[1]]
+
+    with torch.no_grad():
+        unet(x, ts, ctx, Lk, cond_emb=cond, unet_block_indices=taps)      # packs the operands, fills the caches
+        attrs = set(vars(unet))
+        plain, log_plain = logged(lambda: unet(x, ts, ctx, Lk, cond_emb=cond, unet_block_indices=taps))
+        again, log_again = logged(lambda: unet(x, ts, ctx, Lk, cond_emb=cond, unet_block_indices=taps))
+        tape = backward._Tape()
+        taped, log_taped = logged(lambda: unet(x, ts, ctx, Lk, cond_emb=cond, unet_block_indices=taps, tape=tape))
+        assert set(vars(unet)) == attrs
+        dtaps = [torch.ones_like(t.t) for t in plain[1]]
+        _, log_bwd = logged(lambda: backward.unet_backward(unet, x, ts, ctx, Lk, dtaps, taps, cond_emb=cond))
+        with pytest.raises(NotImplementedError):
+            unet(x, ts, ctx, Lk, cond_emb=cond, unet_block_indices=taps, unet_block_indices_type="in",
+                 tape=backward._Tape())
+    for i, (a, b, c) in enumerate(zip(values(plain), values(again), values(taped))):
+        print(dtype, f"output {i}: plain vs plain max |d| {float((a.float() - b.float()).abs().max()):.3e}, "
+                     f"plain vs taped max |d| {float((a.float() - c.float()).abs().max()):.3e}")
+    assert all(torch.equal(a, b) for a, b in zip(values(plain), values(again))), "the plain forward is not bit-repeatable"
+    assert len(values(taped)) == len(values(plain)) == 1 + len(taps)
+    assert all(torch.equal(a, c) for a, c in zip(values(plain), values(taped)))
+    print(dtype, len(log_plain), "forward launches,", len(log_bwd), "with the backward")
+    assert len(log_plain) > 100 and log_again == log_plain and log_taped == log_plain
+    assert len(log_bwd) > len(log_plain) and log_bwd[:len(log_plain)] == log_plain
+
+    # every module once, in forward order
+    recs = tape.records
+    mods = [rec[1] for rec in recs]
+    assert len(set(map(id, mods))) == len(mods) and mods[0] is unet.conv_in
+    # the main path is a chain: every record's input is the record before's output, from the sample to conv_norm_out's input
+    assert recs[0][2] is x and tape.h is recs[-1][-1] and all(b[2] is a[-1] for a, b in zip(recs, recs[1:]))
+    kinds = [rec[0] for rec in recs]
+    assert [m for k, m in zip(kinds, mods) if k == "res"] == unet._resnets()
+    assert [m for k, m in zip(kinds, mods) if k == "tr"] == [m for m in unet.modules() if isinstance(m, Transformer2DModel)]
+    samplers = [s.conv for blk in unet.down_blocks for s in (blk.downsamplers or [])] + \
+               [s.conv for blk in unet.up_blocks for s in (blk.upsamplers or [])]
+    assert [m for k, m in zip(kinds, mods) if k == "conv"] == [unet.conv_in] + samplers and len(samplers) == 6
+    assert len(tape.tapped) == len(taps) and tape.h is not None and tape.e1 is not None and tape.a1 is not None
+
+    # through the extractor and the backbone: the tapes travel by argument, nothing is left on the modules
+    m = extractor
+    m.compute_dtype = m.vae.compute_dtype = m.unet.compute_dtype = dtype
+    gen = BasePromptTimeGenerator(learnable_cond_prompt=True, learnable_cond_time=True, clip_state='no', num_timesteps=1,
+                                  clip_model_name="ViT-L-14-336", ldm_extractor=m, same_cond_params=True)
+    bb = AttentionFeatureExtractorBackbone(
+        attention_features_res=None, feature_dims=[320, 640, 1280], projection_dim=[512, 512, 512],
+        attention_features_location=None, feature_extractor=gen, num_res_blocks=1, out_features=["s3", "s4", "s5"],
+        backbone_in_size=(64, 64))
+    with torch.no_grad():
+        for p in bb.feature_projections.parameters():
+            p.normal_(0.0, 0.02, generator=torch.Generator().manual_seed(3))
+    bb.cuda()
+    images, cond_inputs, cond_emb, _, _ = make_inputs(**CASES["small_t60"])
+    inputs = {"img": images.cuda(), "cond_inputs": cond_inputs.cuda(), "cond_emb": cond_emb.cuda(), "timestep": (60, 61)}
+
+    def run(unet_tape, proj_tape):
+        st = m._stage_encode(inputs)
+        feats = m._stage_unet(st, inputs, tape=unet_tape, _return_tokens=True)
+        bb.forward_features(feats, images.shape[-2:], tape=proj_tape)
+        torch.cuda.synchronize()
+
+    with torch.no_grad():
+        run(None, None)
+        before = [set(vars(o)) for o in (m, m.unet, bb)]
+        unet_tape, proj_tape = backward._Tape(), []
+        run(unet_tape, proj_tape)
+    assert [set(vars(o)) for o in (m, m.unet, bb)] == before
+    assert unet_tape.unet is m.unet and unet_tape.n_enc == 0 and len(unet_tape.records) == len(tape.records)
+    assert [name for _, name, _, _ in proj_tape] == ["s3", "s4", "s5"]
 
 
 def test_ldm_rocm_is_differentiable_through_autograd(cuda):
