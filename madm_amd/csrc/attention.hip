@@ -460,9 +460,7 @@ extern "C" int madm_debug_read_attn_stamps(unsigned long long* host, int n) {
 #endif
 
 // d = 40 at >= 2048 queries: eight-wave workgroups (two query groups per wave) -- round 5, six-slot pipeline, same box, two runs:
-// 372.8 / 373.1 -> 375.3 / 374.7 images/s, serial 8.05 -> 8.01 ms (equal in round 4's pipeline).  MADM_ATTN_NW8=0 for the four-wave form.
-static const bool g_attn_nw8 = [] { const char* e = getenv("MADM_ATTN_NW8"); return !(e && atoi(e) == 0); }();
-static const bool g_attn_nq1 = [] { const char* e = getenv("MADM_ATTN_NQ1"); return e && atoi(e) != 0; }();   // A/B switch
+// 372.8 / 373.1 -> 375.3 / 374.7 images/s, serial 8.05 -> 8.01 ms (equal in round 4's pipeline).
 
 extern "C" int madm_attention_fwd(const madm_attention_args* a, void* stream) {
     MADM_REQUIRE(a && a->q && a->k && a->v && a->o, "attention: null pointer");
@@ -490,7 +488,7 @@ extern "C" int madm_attention_fwd(const madm_attention_args* a, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (a->dtype == MADM_BF16) {
         switch (a->D) {
-            case 40: return a->Lk >= 512 ? (a->Lq >= 2048 && !g_attn_nq1 ? (g_attn_nw8 ? launch_attn<bf16_t, 2, 3, 8, 8, 2>(p, s) : launch_attn<bf16_t, 2, 3, 4, 8, 2>(p, s)) : launch_attn<bf16_t, 2, 3, 4, 8>(p, s))
+            case 40: return a->Lk >= 512 ? (a->Lq >= 2048 ? launch_attn<bf16_t, 2, 3, 8, 8, 2>(p, s) : launch_attn<bf16_t, 2, 3, 4, 8>(p, s))
                                          : launch_attn<bf16_t, 2, 3, 4, 4>(p, s);
             case 64: return launch_attn<bf16_t, 2, 4, 4, 4>(p, s);
             case 80: return a->Lk >= 512 ? launch_attn<bf16_t, 3, 5, 4, 8>(p, s) : launch_attn<bf16_t, 3, 5, 4, 4>(p, s);
@@ -500,7 +498,7 @@ extern "C" int madm_attention_fwd(const madm_attention_args* a, void* stream) {
         }
     } else if (a->dtype == MADM_F16) {
         switch (a->D) {
-            case 40: return a->Lk >= 512 ? (a->Lq >= 2048 && !g_attn_nq1 ? (g_attn_nw8 ? launch_attn<f16_t, 2, 3, 8, 8, 2>(p, s) : launch_attn<f16_t, 2, 3, 4, 8, 2>(p, s)) : launch_attn<f16_t, 2, 3, 4, 8>(p, s))
+            case 40: return a->Lk >= 512 ? (a->Lq >= 2048 ? launch_attn<f16_t, 2, 3, 8, 8, 2>(p, s) : launch_attn<f16_t, 2, 3, 4, 8>(p, s))
                                          : launch_attn<f16_t, 2, 3, 4, 4>(p, s);
             case 64: return launch_attn<f16_t, 2, 4, 4, 4>(p, s);
             case 80: return a->Lk >= 512 ? launch_attn<f16_t, 3, 5, 4, 8>(p, s) : launch_attn<f16_t, 3, 5, 4, 4>(p, s);

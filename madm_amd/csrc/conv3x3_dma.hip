@@ -19,8 +19,8 @@ __device__ unsigned long long g_c3d_stamps[256];
 #define C3D_STAMP(k_)
 #endif
 
-// PERM: weight rows fetched in the permuted channel order of igemm_tile_epilogue (wide epilogue stores, halo_tile_epilogue PERM)
-template <typename T, int BN, bool FUSE, bool PERM>
+// The weight rows are fetched in the permuted channel order of igemm_tile_epilogue (wide epilogue stores, halo_tile_epilogue PERM)
+template <typename T, int BN, bool FUSE>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p, const PatchDecode pd) {
     C3D_STAMP(0);
     kernarg_touch<5>();
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
     for (int i = 0; i < LW; ++i) {
         const int row = (wave * LW + i) * 8 + (lane >> 3);
         const int rr = row & (BN / 2 - 1);   // source-side permutation, as in igemm_glds_kernel: the LDS image does not change
-        const int n = n0 + (PERM ? (row - rr) + ((rr & 15) >> 2) * (4 * NI) + ((rr >> 4) << 2) + (rr & 3) : row);
+        const int n = n0 + ((row - rr) + ((rr & 15) >> 2) * (4 * NI) + ((rr >> 4) << 2) + (rr & 3));
         wvoff[i] = (n < p.N) ? (unsigned)(((size_t)n * p.ldw + ((lane & 7) ^ (row & 7)) * EPC) * sizeof(T)) : OOB;
     }
     IGEMM_OPERAND_DESCRIPTORS(p);
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
     C3D_STAMP(4);
     wait_vmcnt<0>();
     __syncthreads();   // the LDS becomes the statistics scratch of the epilogue
-    halo_tile_epilogue<T, BN, PERM>(p, acc, b, py0, px0, n0, z, reinterpret_cast<float*>(smem_raw));
+    halo_tile_epilogue<T, BN, true>(p, acc, b, py0, px0, n0, z, reinterpret_cast<float*>(smem_raw));
     C3D_STAMP(5);
 #ifdef C3D_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -226,9 +226,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(const IgemmP p
 template <typename T, int BN, bool FUSE>
 int launch_dma_one(const IgemmP& p, hipStream_t s) {
     constexpr size_t lds = (size_t)(HPIX * 8 + 3 * BN * 8) * 16 + 32 * sizeof(float2);
-    if (igemm_wide_epi())
-        return launch_halo_patches<conv3x3_halo_dma_kernel<T, BN, FUSE, true>, BN, TH, TW>(p, lds, s, "conv3x3 (LDS-DMA)", "conv3x3_halo_dma_kernel");
-    return launch_halo_patches<conv3x3_halo_dma_kernel<T, BN, FUSE, false>, BN, TH, TW>(p, lds, s, "conv3x3 (LDS-DMA)", "conv3x3_halo_dma_kernel");
+    return launch_halo_patches<conv3x3_halo_dma_kernel<T, BN, FUSE>, BN, TH, TW>(p, lds, s, "conv3x3 (LDS-DMA)", "conv3x3_halo_dma_kernel");
 }
 
 }  // namespace

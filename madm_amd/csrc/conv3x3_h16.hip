@@ -596,11 +596,7 @@ namespace {
 template <typename T, int BN, bool FUSE, bool WIDE, bool SK = false>
 int launch_h16_one(const IgemmP& p, hipStream_t s) {
     constexpr size_t lds0 = (size_t)((H16_PIX + 7) / 8) * 1024 + 2 * (size_t)BN * 128 + 32 * sizeof(float2);
-    // experiment (MADM_EXP_H16_LDS=<bytes>): ask for more LDS than the kernel uses, e.g. 90112 -> ONE workgroup per CU, the
-    // rest of the CU stays free for the workgroups of kernels on other streams (staged pipeline)
-    static const size_t lds_exp = [] { const char* e = getenv("MADM_EXP_H16_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
-    const size_t lds = lds_exp > lds0 ? lds_exp : lds0;
-    return launch_halo_patches<conv3x3_h16_kernel<T, BN, FUSE, WIDE, SK>, BN, H16_T, H16_T>(p, lds, s, "conv3x3 (16 x 16 patches)",
+    return launch_halo_patches<conv3x3_h16_kernel<T, BN, FUSE, WIDE, SK>, BN, H16_T, H16_T>(p, lds0, s, "conv3x3 (16 x 16 patches)",
                                                                                             "conv3x3_h16_kernel");
 }
 

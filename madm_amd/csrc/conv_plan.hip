@@ -81,12 +81,9 @@ int heuristic_tile(int M, int N, int K) {
     return 3;
 }
 
-// narrowest map the halo kernels take (env MADM_HALO_MIN_W for A/B runs): an 8-wide map wastes half of every 8 x 16 patch,
-// but lets the 8 x 8 UNet level fuse its GroupNorm
-int halo_min_width() {
-    static const int w = [] { const char* e = getenv("MADM_HALO_MIN_W"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : v; }();
-    return w;
-}
+// narrowest map the halo kernels take: an 8-wide map wastes half of every 8 x 16 patch, but lets the 8 x 8 UNet level fuse
+// its GroupNorm
+constexpr int HALO_MIN_W = 8;
 
 int pick_tile_raw(const Request& r) {
     const madm_conv2d_args* a = r.a;
@@ -110,8 +107,7 @@ int pick_tile_raw(const Request& r) {
 // the 16 x 16-patch kernel pays where it fills the chip: at least ~0.75 rounds of its 256-pixel x 128-channel blocks
 // (measured against tile 9 on MI355X, bf16 / f16: +12 .. 23 % on the 512^2 .. 128^2 maps of the VAE, 0.6 x on an 8192-pixel map)
 bool h16_pays(const madm_conv2d_args* a) {
-    static const int off = [] { const char* e = getenv("MADM_NO_H16"); return e ? atoi(e) : 0; }();
-    if (off || a->OH < 16 || a->OW < 16 || a->N < 128) return false;
+    if (a->OH < 16 || a->OW < 16 || a->N < 128) return false;
     const long long blocks = (long long)a->B * ((a->OH + 15) / 16) * ((a->OW + 15) / 16) * ((a->N + 127) / 128);
     return blocks >= 384;
 }
@@ -176,7 +172,7 @@ const Tuned* Request::row(int variant) const {
 // the LDS halo-tile kernel (conv3x3.hip) handles 3x3 / stride 1 / pad 1 convs on maps of at least one patch
 bool halo_eligible(const madm_conv2d_args* a) {
     return a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad_t == 1 && a->pad_l == 1 && !a->upsample &&
-           a->OH == a->IH && a->OW == a->IW && a->OH >= 8 && a->OW >= halo_min_width() && a->epilogue != MADM_EPI_GEGLU;
+           a->OH == a->IH && a->OW == a->IW && a->OH >= 8 && a->OW >= HALO_MIN_W && a->epilogue != MADM_EPI_GEGLU;
 }
 
 // the arguments taken as they stand: the tile madm_conv2d_fwd launches and the split-K its kernels run with (at least one K step

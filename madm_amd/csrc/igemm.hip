@@ -366,8 +366,8 @@ __device__ unsigned long long g_glds_stamps[2048];
 // LIN: 1x1 / stride 1 / no padding / no upsampling (every linear layer and 1x1 conv): output row m reads input row m, so
 // the gather needs no pixel arithmetic -- neither in the set-up (two integer divisions per staged row) nor per DMA
 // instruction (the address is row * ld + channel offset).
-// PERM: the permuted channel mapping of igemm_tile_epilogue (wide epilogue stores); false = MFMA row m of tile j is channel 16 j + m.
-template <typename T, int BM, int BN, int NS, bool LIN, bool PERM>
+// The weight rows are fetched in the permuted channel order of igemm_tile_epilogue's PERM mapping (wide epilogue stores).
+template <typename T, int BM, int BN, int NS, bool LIN>
 __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? (NS == 2 ? 2 : 1) : (NS == 3 && BM == 64 ? 3 : 2)) void igemm_glds_kernel(const IgemmP p) {
 #if defined(__HIP_DEVICE_COMPILE__)   // LDS address-space casts and gfx asm: device pass only (the host needs the stub)
     kernarg_touch<5>();
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? (NS == 2 ? 2 : 1) : (NS
             // fills LDS row (wave half, j, m) asks for the weight row of the channel that MFMA row stands for -- the LDS image and
             // the fragment reads do not change
             const int r = row - BM, rr = r & (BN / 2 - 1);
-            const int n = n0 + (PERM ? (r - rr) + ((rr & 15) >> 2) * (4 * NI) + ((rr >> 4) << 2) + (rr & 3) : r);
+            const int n = n0 + ((r - rr) + ((rr & 15) >> 2) * (4 * NI) + ((rr >> 4) << 2) + (rr & 3));
             if (n < p.N) wvoff[i] = (unsigned)(((size_t)n * p.ldw + swz[i]) * sizeof(T));
         }
     }
@@ -584,7 +584,7 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? (NS == 2 ? 2 : 1) : (NS
 #undef GLDS_LOAD_TILE
     GLDS_BSTAMP(3);
     __syncthreads();   // every wave is done with the last tile: the LDS becomes the statistics scratch
-    igemm_tile_epilogue<T, BM, BN, PERM>(p, acc, m0, n0, z, reinterpret_cast<float*>(gsmem), lns, lnq, cstash, cstash + 256, cstash + 512);
+    igemm_tile_epilogue<T, BM, BN, true>(p, acc, m0, n0, z, reinterpret_cast<float*>(gsmem), lns, lnq, cstash, cstash + 256, cstash + 512);
     GLDS_BSTAMP(4);
 #endif
 }
@@ -751,10 +751,10 @@ __global__ __launch_bounds__(PGN_THREADS) void splitk_groupnorm_kernel(const Ige
     }
 }
 
-template <typename T, int BM, int BN, int NS, bool LIN, bool PERM>
+template <typename T, int BM, int BN, int NS, bool LIN>
 int launch_glds_v(const IgemmP& p, dim3 grid, hipStream_t s) {
     constexpr size_t lds = (size_t)NS * (BM + BN) * 128;
-    auto kern = igemm_glds_kernel<T, BM, BN, NS, LIN, PERM>;
+    auto kern = igemm_glds_kernel<T, BM, BN, NS, LIN>;
     static std::atomic<uint64_t> attr_done{0};
     if (int e = madm_raise_dynamic_lds(reinterpret_cast<const void*>(kern), (size_t)(lds), attr_done, "igemm (LDS-DMA)")) return e;
     kern<<<grid, 256, lds, s>>>(p);
@@ -766,9 +766,7 @@ int launch_glds_v(const IgemmP& p, dim3 grid, hipStream_t s) {
 template <typename T, int CODE, int BM, int BN, TileFamily F, int SLOTS>
 int launch_gemm_tile(const IgemmP& p, dim3 grid, hipStream_t s, bool lin) {
     if constexpr (F == GLDS) {
-        if (igemm_wide_epi())
-            return lin ? launch_glds_v<T, BM, BN, SLOTS, true, true>(p, grid, s) : launch_glds_v<T, BM, BN, SLOTS, false, true>(p, grid, s);
-        return lin ? launch_glds_v<T, BM, BN, SLOTS, true, false>(p, grid, s) : launch_glds_v<T, BM, BN, SLOTS, false, false>(p, grid, s);
+        return lin ? launch_glds_v<T, BM, BN, SLOTS, true>(p, grid, s) : launch_glds_v<T, BM, BN, SLOTS, false>(p, grid, s);
     } else if constexpr (F == IGEMM) {
         if constexpr (CODE == 2 || CODE == 3) {
             if (lin) {

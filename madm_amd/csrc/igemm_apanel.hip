@@ -71,10 +71,9 @@ template <> __device__ __forceinline__ void ap_store2<bf16_t>(__amdgpu_buffer_rs
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), rs, off, 0, 0);
 }
 
-// WM = waves along the rows: 2 -> 2 x 2 waves, wave tile (BM / 2) x 32; 1 -> 1 x 4 waves, wave tile BM x 16.
+// 1 x 4 waves, wave tile BM x 16.
 // After the prologue the waves never synchronise: the panel is read-only and every wave streams the weight rows of ITS
-// columns into a private ring (with WM = 2 the two waves of a column half fetch the same rows: twice the weight bytes on
-// the load path, still half of what a 64 x 64 tile moves per FLOP, and no barrier in the loop).
+// columns into a private ring (no barrier in the loop).
 // Built WITHOUT packed-FP32 VALU ops (device pass only; see csrc/Makefile's note for what was observed with them).
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(AP_PKCHECK)
 #define AP_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
@@ -87,14 +86,13 @@ template <> __device__ __forceinline__ void ap_store2<bf16_t>(__amdgpu_buffer_rs
 __device__ unsigned g_ap_pk[1024];
 #endif
 
-template <typename T, int BM, int WM>
+template <typename T, int BM>
 __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(const IgemmP p, int tpb, int nchunks) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int EPC = TT<T>::EPC;
-    constexpr int WN = 4 / WM;
-    constexpr int WCOLS = AP_BN / WN;                    // columns per wave: 32 / 16
-    constexpr int MI = BM / (16 * WM), NI = WCOLS / 16;
-    constexpr int WP = WCOLS / 8;                        // DMA pieces (8 rows x 128 B) per wave and step: 4 / 2
+    constexpr int WCOLS = AP_BN / 4;                     // columns per wave: 16
+    constexpr int MI = BM / 16, NI = WCOLS / 16;
+    constexpr int WP = WCOLS / 8;                        // DMA pieces (8 rows x 128 B) per wave and step: 2
     constexpr unsigned SLOT = WCOLS * 128u;              // bytes per ring slot
     constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) uint4 apsmem[];   // [KC][BM][8] panel | [4 waves][NS][WCOLS][8] | bias
@@ -102,7 +100,7 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = (WM == 2) ? (wave >> 1) : 0, wn = (WM == 2) ? (wave & 1) : wave;
+    const int wn = wave;
     const int KC = p.nk;                                  // 128-byte chunks per row
     const int bid = xcd_block_order();
     const int P = (p.M + BM - 1) / BM;
@@ -258,7 +256,7 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const int c = (fg + 4 * kk) ^ fsw;
-            aA[kk] = base + (unsigned)(((wm * (BM / WM) + frow) * 8 + c) * 16);
+            aA[kk] = base + (unsigned)((frow * 8 + c) * 16);
             aB[kk] = base + panel_bytes + (unsigned)wave * (AP_NS * SLOT) + (unsigned)((frow * 8 + c) * 16);
         }
     }
@@ -346,7 +344,7 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
             landed = (S - 1 - s < AP_NS - 1) ? S - 1 - s : AP_NS - 1;
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
-                const int m = m0 + wm * (BM / WM) + i * 16 + frow;
+                const int m = m0 + i * 16 + frow;
 #pragma unroll
                 for (int j = 0; j < NI; ++j) {
                     const int n = nb + 16 * j;
@@ -366,13 +364,12 @@ __global__ __launch_bounds__(256, 2) AP_NO_PACKED_F32 void igemm_apanel_kernel(c
 #endif
 }
 
-template <typename T, int BM, int WM>
+template <typename T, int BM>
 int launch_apanel_bm(const IgemmP& p, hipStream_t s) {
     const int KC = p.nk;
-    const size_t lds = (size_t)KC * BM * 128 + (size_t)4 * AP_NS * (AP_BN / (4 / WM)) * 128 +
+    const size_t lds = (size_t)KC * BM * 128 + (size_t)4 * AP_NS * (AP_BN / 4) * 128 +
                        (size_t)AP_MAX_TPB * AP_BN * sizeof(float);
-    static const size_t pad = [] { const char* e = getenv("MADM_APANEL_LDS_PAD"); return e ? (size_t)atol(e) : (size_t)0; }();
-    auto kern = igemm_apanel_kernel<T, BM, WM>;
+    auto kern = igemm_apanel_kernel<T, BM>;
     static std::atomic<uint64_t> attr_set{0};   // per device (the attribute is)
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -389,14 +386,14 @@ int launch_apanel_bm(const IgemmP& p, hipStream_t s) {
     const int P = (p.M + BM - 1) / BM;
     const int tilesN = (p.N + AP_BN - 1) / AP_BN;
     // one round of workgroups (one per CU: the panel takes half the LDS), at most AP_MAX_TPB column tiles each
-    static const int target = [] { const char* e = getenv("MADM_APANEL_BLOCKS"); return e ? atoi(e) : 512; }();
+    constexpr int target = 512;
     int nsplit = (target + P - 1) / P;
     if (nsplit > tilesN) nsplit = tilesN;
     if (nsplit < 1) nsplit = 1;
     int tpb = (tilesN + nsplit - 1) / nsplit;
     if (tpb > AP_MAX_TPB) tpb = AP_MAX_TPB;
     const int nchunks = (tilesN + tpb - 1) / tpb;
-    kern<<<dim3((unsigned)(P * nchunks)), 256, lds + pad, s>>>(p, tpb, nchunks);
+    kern<<<dim3((unsigned)(P * nchunks)), 256, lds, s>>>(p, tpb, nchunks);
     return madm_check_launch("igemm_apanel_kernel");
 }
 
@@ -404,9 +401,7 @@ int launch_apanel_bm(const IgemmP& p, hipStream_t s) {
 
 // rows the panel may hold for this reduction width, or 0 when the layer does not fit (row bytes x BM <= 80 KB)
 int igemm_apanel_bm(int K, int esize) {
-    static const int force = [] { const char* e = getenv("MADM_APANEL_BM"); return e ? atoi(e) : 0; }();
     const size_t row = (size_t)K * esize;
-    if (force && row * force <= 96 * 1024) return force;
     // 40 KB panels where the rows allow it: two workgroups per CU (72 KB each with the rings) overlap each other's
     // prologue / epilogue / DMA issue -- measured on MI355X, f16: GEGLU 8192 x 320 -> 2560  36.0 us against 40.8 us with
     // one 128-row panel per CU (and 40.3 us for the 128 x 64 igemm tile)
@@ -419,9 +414,8 @@ int igemm_apanel_bm(int K, int esize) {
 template <typename T>
 int launch_igemm_apanel(const IgemmP& p, hipStream_t s) {
     const int bm = igemm_apanel_bm(p.K, (int)sizeof(T));
-    if (bm == 128) return launch_apanel_bm<T, 128, 2>(p, s);
-    if (bm == 64) return launch_apanel_bm<T, 64, 1>(p, s);
-    if (bm == 32) return launch_apanel_bm<T, 32, 1>(p, s);
+    if (bm == 64) return launch_apanel_bm<T, 64>(p, s);
+    if (bm == 32) return launch_apanel_bm<T, 32>(p, s);
     madm_set_error("igemm (A panel): K = %d does not fit the panel", p.K);
     return MADM_ERR_UNSUPPORTED;
 }

@@ -334,13 +334,6 @@ template <typename T> __device__ __forceinline__ void load8(const T* p, f32x4& a
     }
 }
 
-// MADM_IGEMM_WIDE_EPI=0: the LDS-DMA kernels (igemm_glds_kernel, conv3x3_halo_dma_kernel) keep the plain channel mapping and the
-// per-chunk epilogue stores (A/B runs); read once.
-inline bool igemm_wide_epi() {
-    static const bool on = [] { const char* e = getenv("MADM_IGEMM_WIDE_EPI"); return !(e && atoi(e) == 0); }();
-    return on;
-}
-
 // Permuted mapping (CS = 4): may this LAUNCH move a lane's contiguous span in wide pieces?  Block-uniform, from the launch
 // parameters alone.  A wide piece covers GU chunks under GEGLU (2 * GU outputs: 8 bytes at NI = 2, 16 at NI = 4 in the 16-bit
 // modes, 16 in f32) and two chunks otherwise (16 bytes, 16-bit modes only: an f32 chunk is a 16-byte store already).  It needs

@@ -1,6 +1,6 @@
 // {dtype (0 f32, 1 bf16), M, N, K, KH, variant (0 plain, 1 GroupNorm-fused, 2 upsample, 3 stride 2), tile (1..17: the table g_tiles of igemm.hip), splitk}
 // measured by tools/tune_insitu.py on MI355X (whole eager forwards, cold weights), bf16, round 1; plain and
-// GroupNorm-fused variants come from runs under different fusion policies (MADM_FUSE_GN_MAX_N)
+// GroupNorm-fused variants come from runs under different fusion policies (ops.FUSE_GN_MAX_N)
 // -- feature extractor, bs=2, 512x512 (BASELINE configs[1])
 {1, 2, 1280, 320, 1, 0, 11, 1},   // r5 side-by-side: side 2.4 -> 2.1 us, alone 5.2 -> 4.1 (was tile 6)
 {1, 2, 1280, 1280, 1, 0, 7, 8},

@@ -79,8 +79,7 @@ class MTMADISE(MadmInference):
         # student trails the teacher layer by layer and the step is 0.4 .. 1.4 % SLOWER than in line (same box, three runs each:
         # 228.8 / 227.9 / 234.1 vs 225.7 / 224.4 / 233.1 ms, profiles/round6_ab_train_teacher_stream.txt); round 5's +1.5 % was
         # measured with the race in place.  MADM_TEACHER_OVERLAP=1 switches it on (tested: tests/test_train_gpu.py).
-        self.overlap_teacher = bool(int(os.environ.get("MADM_TEACHER_OVERLAP", "0"))) and \
-            not bool(int(os.environ.get("MADM_NO_TEACHER_OVERLAP", "0")))
+        self.overlap_teacher = bool(int(os.environ.get("MADM_TEACHER_OVERLAP", "0")))
         self._teacher_stream, self._teacher_warm = None, set()
         self.blur, self.color_jitter_strength, self.color_jitter_probability = blur, color_jitter_strength, color_jitter_probability
         self.enable_mixup, self.pl_crop, self.color_aug_flag = enable_mixup, pl_crop, color_aug_flag
@@ -271,7 +270,7 @@ class MTMADISE(MadmInference):
         # result is needed only where the labels are mixed: it runs on a side stream beside the two student forwards (from the
         # second step on: the first builds the shared packed operands of the frozen modules in one stream).  Same kernels,
         # same values; the Python-side random draws keep their order (random: two uniforms above, this randint; numpy: the
-        # class choices below).  MADM_NO_TEACHER_OVERLAP=1 for A/B runs.
+        # class choices below).
         main_stream = torch.cuda.current_stream(source.device)
         # ... per input geometry: a batch / crop size seen for the first time (a short last batch) runs in line, so whatever a
         # first pass at that size builds lazily is built in ONE stream; the shared constant caches are stream-safe on top of

@@ -150,7 +150,7 @@ class Conv2d(_Packed):
         wp, b = self.packed(dtype, splits)
         OH, OW = self.out_hw(x.H, x.W, upsample)
         pad = 0 if self.asym_pad else self.padding
-        st = ops.new_chsums(x.B, self.n_pad, x.t.device) if (stats and not ops.EXP_NO_STATS) else None
+        st = ops.new_chsums(x.B, self.n_pad, x.t.device) if stats else None
         post_gn = None
         if post_norm is not None:
             assert self.n_pad == self.out_channels and residual is None

@@ -6,7 +6,6 @@ channels-last 2-D tensors ``[B*H*W, C]``.  There is no fallback path.
 """
 import ctypes
 import os
-import re
 
 import torch
 
@@ -135,29 +134,16 @@ PROFILE = None
 # cancelled -- no overhead estimate to subtract (bench.py's roofline; the pass's results are thrown away: fused
 # statistics are accumulated three times).
 PROFILE_DIFF = False
-EXP_NO_STATS = bool(int(os.environ.get('MADM_EXP_NO_STATS', '0')))   # timing experiment only
-# tools/tune_insitu.py: split-K factor forced on every small-M launch (env MADM_EXP_SPLITK: e.g. 1 = no split-K anywhere)
-FORCE_SPLITK = int(os.environ["MADM_EXP_SPLITK"]) if os.environ.get("MADM_EXP_SPLITK") else None
-# timing experiments only (results become garbage): launches of the named classes are skipped -- "layernorm", "gn_apply",
-# "attention", "softmax", or tile codes of madm_conv2d_plan ("tile7", ...): what would the step cost without them?
-EXP_SKIP = set(filter(None, os.environ.get("MADM_EXP_SKIP", "").split(",")))
-_SKIP_RE = [re.compile(t[3:]) for t in EXP_SKIP if t.startswith("re:")]
-
-
-def _skip_match(desc):
-    return any(r.search(desc) for r in _SKIP_RE)
-
-
+# tools/tune_insitu.py: split-K factor forced on every small-M launch (e.g. 1 = no split-K anywhere)
+FORCE_SPLITK = None
 # When TILE_LOG is a list, every forward conv / linear launch appends (description, tile code, split-K, plan.tuned_row, FLOPs):
 # tests/test_parity_gpu.py::test_bench_workloads_have_tuned_rows
 TILE_LOG = None
 FUSE_GN = True   # fold GroupNorm(+SiLU) into eligible 3x3 convs (debug switch)
-# the GroupNorm that consumes a split-K conv rides on its reduction (conv2d(post_gn=...)); env MADM_NO_POST_GN for A/B runs
-POST_GN = not bool(int(os.environ.get("MADM_NO_POST_GN", "0")))
-FUSE_GN_MAX_N = int(os.environ.get("MADM_FUSE_GN_MAX_N", "256"))   # ... whose output has at most 256 channels: the
+FUSE_GN_MAX_N = 256   # ... whose output has at most 256 channels: the
 # transform is redone once per output-channel tile, so on the wide UNet layers (320 .. 1280 channels, 5 .. 20 tiles of 64) a
 # stand-alone GroupNorm pass + the plain conv is less total work.  Same-box A/B with both variants tuned (images/s,
-# overlapped / serial): 128 -> 269 / 220, 256 -> 270 / 220, unlimited -> 262 / 221.  Env override for A/B runs.
+# overlapped / serial): 128 -> 269 / 220, 256 -> 270 / 220, unlimited -> 262 / 221.
 
 
 def can_fuse_groupnorm(IH, IW, KH, stride, pad, asym_pad, upsample):
@@ -293,7 +279,7 @@ def conv2d(x1, w, B, IH, IW, *, N, x2=None, KH=1, KW=1, stride=1, pad_t=0, pad_l
         _need_cuda(gamma, beta)
         assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.is_contiguous() and beta.is_contiguous()
         assert gamma.numel() == N and beta.numel() == N and residual is None and ln is None
-        a.pn_groups = int(groups) if POST_GN else 0
+        a.pn_groups = int(groups)
     if stats is not None:
         assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == B * N * 2
         a.stats = stats.data_ptr()
@@ -307,11 +293,6 @@ def conv2d(x1, w, B, IH, IW, *, N, x2=None, KH=1, KW=1, stride=1, pad_t=0, pad_l
     if plan.workspace_bytes:
         ws = _workspace(plan.workspace_bytes, x1.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    if EXP_SKIP:
-        # timing experiments only (tools/exp/skip_sensitivity.sh): "tileN", or "re:<regex>" on "k<KH> s<stride> M.. N.. K.."
-        if ("tile%d" % plan.tile) in EXP_SKIP or _skip_match(
-                f"k{KH} s{stride}{' up' if upsample else ''} M{M} N{N} K{KH * KW * (C1 + C2)}"):
-            return out if post_gn is None else (out, applied)
     if TILE_LOG is not None:
         TILE_LOG.append((f"dt{a.dtype} M{M} N{N} K{KH * KW * (C1 + C2)} k{KH} s{stride}{' up' if upsample else ''}"
                          f"{' gn' if gn is not None else ''}", plan.tile, plan.splitk, bool(plan.tuned_row),
@@ -617,7 +598,7 @@ def groupnorm(xs, B, HW, G, gamma, beta, eps, silu=False, stats=None, act=None, 
     C1 = xs[0].shape[1]
     s2 = stats[1].data_ptr() if len(xs) > 1 else None
     off = 0
-    if len(xs) == 2 and residual is None and "gn_apply" not in EXP_SKIP:      # both sources in one launch
+    if len(xs) == 2 and residual is None:      # both sources in one launch
         assert xs[0].is_contiguous() and xs[1].is_contiguous()
         check(lib.madm_groupnorm_apply_cat(dtype_code(xs[0]), xs[0].data_ptr(), xs[1].data_ptr(), out.data_ptr(), out.stride(0),
                                            B, HW, C1, xs[1].shape[1], G, stats[0].data_ptr(), s2, gamma.data_ptr(),
@@ -626,8 +607,6 @@ def groupnorm(xs, B, HW, G, gamma, beta, eps, silu=False, stats=None, act=None, 
         return out
     for x in xs:
         assert x.is_contiguous()
-        if "gn_apply" in EXP_SKIP:
-            break
         check(lib.madm_groupnorm_apply(dtype_code(x), x.data_ptr(), out.data_ptr(), out.stride(0), B, HW, x.shape[1],
                                        off, Ctot, G, stats[0].data_ptr(), C1, s2, gamma.data_ptr(), beta.data_ptr(),
                                        float(eps), _act_code(silu, act), _ptr(residual),
@@ -710,8 +689,6 @@ def layernorm(x, gamma, beta, eps, out=None):
     assert x.is_contiguous() and x.dim() == 2
     if out is None:
         out = torch.empty_like(x)
-    if "layernorm" in EXP_SKIP:
-        return out
     check(lib.madm_layernorm_fwd(dtype_code(x), x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1],
                                  gamma.data_ptr(), beta.data_ptr(), float(eps), _stream()),
           "madm_layernorm_fwd")
@@ -732,8 +709,6 @@ def attention(q, k, v, B, H, Lq, Lk, D, scale, out=None):
     a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
     a.B, a.H, a.Lq, a.Lk, a.D = B, H, Lq, Lk, D
     a.scale = float(scale)
-    if "attention" in EXP_SKIP or (EXP_SKIP and _skip_match(f"attn d{D} Lq{Lq} Lk{Lk}")):
-        return out
     with _Prof(f"attn_d{D}" + _SUFFIX[q.dtype], 4.0 * B * H * Lq * Lk * D,
                f"B{B} H{H} Lq{Lq} Lk{Lk}") as pr:
         check(lib.madm_attention_fwd(ctypes.byref(a), _stream()), "madm_attention_fwd")

@@ -10,13 +10,8 @@ optimizer step every packed operand is re-derived, and as torch ops that was 2 2
 import torch
 
 
-import os
-
-_TORCH_PACK = bool(int(os.environ.get("MADM_TORCH_PACK", "0")))     # A/B runs: the torch statements on the GPU, as before
-
-
 def _hip(w):
-    return w.is_cuda and w.dtype == torch.float32 and not _TORCH_PACK
+    return w.is_cuda and w.dtype == torch.float32
 
 
 def round_up(x, m):

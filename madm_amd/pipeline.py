@@ -278,34 +278,12 @@ class StagedExtractor(_SlotRunner):
         if streams is not None:       # reuse another (idle) pipeline's streams: they already sit on pipes of their own
             assert len(streams) == self.k + 1
             self.s_enc, self.s_unet = streams[0], list(streams[1:])
-        elif os.environ.get("MADM_EXP_CUMASK"):
-            # experiment: "<enc_lo>-<enc_hi>,<unet_lo>-<unet_hi>" = CU ranges (of 256) the encoder stream / the UNet streams may
-            # use (hipExtStreamCreateWithCUMask): does keeping the chip-filling encoder kernels off some CUs shorten the wait
-            # of the UNet's small grids for slots?  
-            import ctypes
-            hip = ctypes.CDLL("libamdhip64.so")
-
-            def masked(lo, hi):
-                words = (ctypes.c_uint32 * 8)()
-                for b_ in range(lo, hi):
-                    words[b_ // 32] |= 1 << (b_ % 32)
-                st = ctypes.c_void_p()
-                rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(st), 8, words)
-                assert rc == 0, f"hipExtStreamCreateWithCUMask failed: {rc}"
-                return torch.cuda.ExternalStream(st.value, device=dev)
-            enc, un = os.environ["MADM_EXP_CUMASK"].split(",")
-            e0, e1 = (int(v) for v in enc.split("-"))
-            u0, u1 = (int(v) for v in un.split("-"))
-            self.s_enc = masked(e0, e1)
-            self.s_unet = [masked(u0, u1) for _ in range(self.k)]
         else:
             # the encoder stream at high priority: its chip-filling kernels are the pipeline's pacemaker, and with six slots the
             # UNet streams always have work queued behind them (round 5, same box, two runs: 372.6 / 372.2 -> 377.6 / 377.7
             # images/s; UNet streams high instead: 370.2 / 369.6; round 3's three-slot pipeline: 307.9 vs 311.6 without).
-            # MADM_EXP_PRIO: "e" (default) / "u" = UNet streams high / "0" = all equal
-            prio = os.environ.get("MADM_EXP_PRIO", "e")
-            self.s_enc = torch.cuda.Stream(device=dev, priority=-1 if prio == "e" else 0)
-            self.s_unet = [torch.cuda.Stream(device=dev, priority=-1 if prio == "u" else 0) for _ in range(self.k)]
+            self.s_enc = torch.cuda.Stream(device=dev, priority=-1)
+            self.s_unet = [torch.cuda.Stream(device=dev, priority=0) for _ in range(self.k)]
         # per-slot static inputs: the graphs read THESE tensors; everything that is not a tensor is a capture-time constant
         self.tensor_keys = [k_ for k_ in ('img', 'cond_inputs', 'cond_emb') if k_ in example_inputs]
         self.const_inputs = {k_: v for k_, v in example_inputs.items() if k_ not in self.tensor_keys}

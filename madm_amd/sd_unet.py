@@ -9,8 +9,6 @@ is a K-concatenated side GEMM.
 """
 import math
 
-import os
-
 import torch
 import torch.nn as nn
 
@@ -23,9 +21,9 @@ LORA_PAD = 64  # K-extension of a LoRA-augmented GEMM (>= sum of the fused ranks
 
 
 # The transformer block's last linear layer (ff.net[2] + residual) composed with Transformer2DModel.proj_out (+ residual): one
-# two-source GEMM [h2 | g] [Wp | Wp Wf]^T instead of two launches (16 per UNet forward); MADM_NO_FUSE_PROJ_OUT=1 for A/B runs
-FUSE_PROJ_OUT = not bool(int(os.environ.get("MADM_NO_FUSE_PROJ_OUT", "0")))
-FOLD_LN = not bool(int(os.environ.get("MADM_NO_FOLD_LN", "0")))   # LayerNorm folded into its consumer GEMM (A/B switch)
+# two-source GEMM [h2 | g] [Wp | Wp Wf]^T instead of two launches (16 per UNet forward).  False = the two-launch path
+# (tests/test_parity_gpu.py uses it as the reference of the composed one)
+FUSE_PROJ_OUT = True
 
 
 # ----------------------------------------------------------------------------- LoRA
@@ -246,19 +244,19 @@ class BasicTransformerBlock(nn.Module):
         self.ff = FeedForward(dim)
 
     def forward(self, h, B, L, ctx, Lk, defer_ff_out=False):
-        """The three LayerNorms are folded into the GEMMs that consume them (QKV, cross-attention Q, GEGLU projection:
-        FOLD_LN) -- 48 launches per UNet forward less; with an active LoRA adapter on a consuming projection the norm runs
+        """The three LayerNorms are folded into the GEMMs that consume them (QKV, cross-attention Q, GEGLU
+        projection) -- 48 launches per UNet forward less; with an active LoRA adapter on a consuming projection the norm runs
         as its own pass (the adapter's skinny GEMM reads the normalised rows)."""
         a1, a2 = self.attn1, self.attn2
-        f1 = FOLD_LN and not a1._fused("_f_qkv", ("to_q", "to_k", "to_v")).has_active_lora()
+        f1 = not a1._fused("_f_qkv", ("to_q", "to_k", "to_v")).has_active_lora()
         h = a1(h if f1 else self.norm1(h), B, L, residual=h, ln=self.norm1 if f1 else None)
         kv = ctx.kv.get(id(a2)) if isinstance(ctx, CtxKV) else None
-        f2 = FOLD_LN and not a2._fused("_f_q", ("to_q",)).has_active_lora()
+        f2 = not a2._fused("_f_q", ("to_q",)).has_active_lora()
         h = a2(h if f2 else self.norm2(h), B, L, ctx=ctx.t if isinstance(ctx, CtxKV) else ctx, Lk=Lk, residual=h, kv=kv,
                ln=self.norm2 if f2 else None)
         if defer_ff_out:    # Transformer2DModel folds ff.net[2] into its proj_out: hand back the stream and the GEGLU output
-            return h, self.ff.net[0](h if FOLD_LN else self.norm3(h), ln=self.norm3 if FOLD_LN else None)
-        h = self.ff(h if FOLD_LN else self.norm3(h), residual=h, ln=self.norm3 if FOLD_LN else None)
+            return h, self.ff.net[0](h, ln=self.norm3)
+        h = self.ff(h, residual=h, ln=self.norm3)
         return h
 
 
@@ -307,13 +305,13 @@ class Transformer2DModel(nn.Module):
         h = self.proj_in(self.norm(x), stats=False)
         t = h.t
         # the composed operand reads ff.net[2]'s own weight: a plain Linear only (an adapter wrapped around it -- a LoRA config
-        # whose target_modules match 'net.2' -- takes the two-launch path, as the FOLD_LN paths do)
+        # whose target_modules match 'net.2' -- takes the two-launch path, as the folded-LayerNorm paths do)
         if (FUSE_PROJ_OUT and len(self.transformer_blocks) == 1 and self.proj_out.n_pad == self.proj_out.out_channels
                 and type(self.transformer_blocks[0].ff.net[2]) is Linear and self._proj_out_ff_stable()):
             h2, g = self.transformer_blocks[0](t, x.B, x.HW, ctx, Lk, defer_ff_out=True)
             wp, b = self._proj_out_ff_operand(h2.dtype)
             C = self.proj_out.out_channels
-            st = None if ops.EXP_NO_STATS else ops.new_chsums(x.B, C, h2.device)
+            st = ops.new_chsums(x.B, C, h2.device)
             o = ops.conv2d(h2, wp, x.B, x.H, x.W, N=C, x2=g, bias=b, residual=x.t, stats=st, alg_nk=(C, 5 * h2.shape[1]))
             return Tok(o, x.B, x.H, x.W, st)
         for blk in self.transformer_blocks:

@@ -498,7 +498,7 @@ def test_tile_names_are_the_kernel_classes_bench_keys_on():
 def test_can_fuse_groupnorm_asks_the_library_and_keeps_its_rule():
     """ops.can_fuse_groupnorm asks madm_conv2d_can_fuse_groupnorm; the rule it restated in Python up to ABI 5 stays here as the reference."""
     from madm_amd import ops
-    assert "MADM_HALO_MIN_W" not in os.environ and ops.FUSE_GN
+    assert ops.FUSE_GN
     n = 0
     for IH in range(4, 33):
         for IW in range(4, 33):
@@ -540,8 +540,7 @@ def test_conv_plans_replay_the_recorded_decisions():
     assert [f[0] for f in tool.Args._fields_] == [f[0] for f in _lib.Conv2dArgs._fields_]
     assert ctypes.sizeof(tool.Args) == ctypes.sizeof(_lib.Conv2dArgs)
     assert tool.Plan._fields_ == _lib.Conv2dPlan._fields_
-    for env in ("MADM_TUNED_FILE", "MADM_HALO_MIN_W", "MADM_NO_H16"):
-        assert env not in os.environ, env
+    assert "MADM_TUNED_FILE" not in os.environ
     want = json.load(open(tool.FIXTURE))
     assert len(want["explicit"]) >= 200 and all(len(c) == len(want["fields"]) for c in want["explicit"])
     lib = tool.open_lib(_lib.LIB_PATH, "new")
@@ -553,3 +552,23 @@ def test_conv_plans_replay_the_recorded_decisions():
     # the grid reaches every tile code and both outcomes of every boolean
     assert tiles == set(range(1, 18)) and all(s == {0, 1} for s in seen), (tiles, seen)
     assert lib.madm_get_tuning_profile() == 0
+
+
+def test_readme_lists_every_environment_switch():
+    """Every MADM_* environment variable the package reads (os.environ[...] / os.environ.get(...) in madm_amd/**/*.py, getenv("...") in
+    madm_amd/csrc/*) has a row in the README's "Environment variables" table, and the table names nothing the code does not read: a
+    switch is a second configuration of the product, so it is either documented or not there."""
+    import glob
+    read = set()
+    for f in glob.glob(os.path.join(ROOT, "madm_amd", "**", "*.py"), recursive=True):
+        read |= set(re.findall(r"""os\.environ(?:\.get\(|\[)\s*["'](MADM_[A-Z0-9_]+)["']""", open(f).read()))
+    csrc = [f for f in glob.glob(os.path.join(ROOT, "madm_amd", "csrc", "*")) if os.path.isfile(f) and not f.endswith((".o", ".so"))]
+    assert csrc
+    for f in csrc:
+        read |= set(re.findall(r"""getenv\(\s*"(MADM_[A-Z0-9_]+)"\s*\)""", open(f, errors="replace").read()))
+    assert "MADM_HIP_LIB" in read and "MADM_TUNED_FILE" in read      # both scans find something
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    assert readme.count("## Environment variables") == 1
+    section = readme.split("## Environment variables", 1)[1].split("\n## ", 1)[0]
+    table = set(re.findall(r"^\| `(MADM_[A-Z0-9_]+)` \|", section, flags=re.M))
+    assert table == read, f"undocumented: {sorted(read - table)}; documented but not read: {sorted(table - read)}"

@@ -623,7 +623,7 @@ def test_trainer_step_through_rccl_single_rank(cuda, monkeypatch):
                          ids=["f32-frozen", "f16-frozen", "f32-lr1e-4"])
 def test_teacher_side_stream_is_bit_identical_over_steps(cuda, dtype, lr):
     """the EMA teacher's forward on a side stream (MTMADISE.overlap_teacher, from the SECOND step of an
-    input geometry on) against the same steps in line (MADM_NO_TEACHER_OVERLAP=1 semantics): five seeded optimizer steps --
+    input geometry on) against the same steps in line (the default): five seeded optimizer steps --
     the fourth with a SHORT batch (B = 1: a geometry seen for the first time after the warm-up, lazily built constants of
     that size) and the fifth at the first geometry again.
     lr = 0 ('frozen': AdamW runs, the weights stand still, the EMA teacher still moves deterministically): the FORWARD of a step

@@ -63,7 +63,7 @@ def main():
                 "2=128x64, 3=64x64 igemm; 4 / 5 = halo conv3x3 x128 / x64; 6 = 64x64 igemm, 8-deep prefetch; 7 / 8 / 11 = "
                 "LDS-DMA igemm 64x64 / 128x64 / 64x64 short ring; 9 / 10 = LDS-DMA halo x128 / x64), splitk}\n")
         f.write("// measured by tools/tune_insitu.py on MI355X (whole eager forwards, cold weights), bf16, round 1; plain and\n"
-                "// GroupNorm-fused variants come from runs under different fusion policies (MADM_FUSE_GN_MAX_N)\n")
+                "// GroupNorm-fused variants come from runs under different fusion policies (ops.FUSE_GN_MAX_N)\n")
         f.write("// -- feature extractor, bs=2, 512x512 (BASELINE configs[1])\n")
         for r in extract:
             f.write("{%d, %d, %d, %d, %d, %d, %d, %d},\n" % r)

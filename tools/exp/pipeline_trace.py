@@ -3,7 +3,7 @@
 flight, and for the heavy kernel classes the share of their run time during which another queue's kernel also ran.
 FINDING (round 3): under --kernel-trace the queues do not overlap at all -- 96.6 % of the pipelined window has exactly ONE
 kernel in flight and a step takes 22 ms instead of 6.2: the profiler serialises dispatches, so the pipeline's overlap cannot be
-read off a kernel trace (use tools/exp/skip_sensitivity.sh instead).
+read off a kernel trace.
 usage: pipeline_trace.py <dir | kernel_trace.csv>"""
 import collections
 import csv

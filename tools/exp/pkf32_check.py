@@ -4,7 +4,6 @@ igemm_apanel.hip (build/libmadm_hip_pkcheck.so: the A-stationary kernel WITH pac
 re-derived by scalar v_sub_f32 / v_mul_f32 from the same registers inside the kernel, mismatches are recorded):
 
     MADM_HIP_LIB=build/libmadm_hip_pkcheck.so python tools/exp/pkf32_check.py [--reps 40]
-    MADM_APANEL_LDS_PAD=90000 MADM_HIP_LIB=... python tools/exp/pkf32_check.py      (control: one workgroup per CU)
 
 Prints, per shape: wrong output elements against a torch reference, the in-kernel mismatch count, and the decoded records
 (lane, piece round u, EXEC mask, operand and result bits, hardware id)."""
@@ -34,7 +33,7 @@ def main():
     dtype = {"f16": torch.float16, "bf16": torch.bfloat16}[args.dtype]
     raw = ctypes.CDLL(LIB_PATH)
     has = hasattr(raw, "madm_debug_read_ap_pkcheck")
-    print("lib", LIB_PATH, "pkcheck export:", has, "LDS pad", os.environ.get("MADM_APANEL_LDS_PAD", "0"))
+    print("lib", LIB_PATH, "pkcheck export:", has)
     buf = (ctypes.c_uint * 1024)()
     if has:
         raw.madm_debug_read_ap_pkcheck(buf, 1024, 1)

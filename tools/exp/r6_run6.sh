@@ -13,4 +13,4 @@ timeout 900 python -m pytest -q -p no:cacheprovider tests/test_parity_gpu.py -k 
 echo "parity rc=$? $(grep -E ' passed| failed' $O/parity.log | tail -1)"; grep -E "^FAILED|^E  " $O/parity.log | head -20
 timeout 600 python tools/exp/train_aten_sites.py > $O/train_aten_sites.txt 2>&1; head -60 $O/train_aten_sites.txt
 python bench.py --workload train --steps 5 --warmup 2 2>/dev/null | cut -c1-600
-MADM_NO_TEACHER_OVERLAP=1 python bench.py --workload train --steps 5 --warmup 2 2>/dev/null | cut -c1-600
+MADM_TEACHER_OVERLAP=1 python bench.py --workload train --steps 5 --warmup 2 2>/dev/null | cut -c1-600
