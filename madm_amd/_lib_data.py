@@ -1,31 +1,23 @@
 """ctypes binding of libmadm_data.so (the C ABI declared in include/madm_data.h): the dataset pipeline's kernels and the
 PNG reader's unfilter loop.  Loaded by ``madm_amd/data.py`` and ``madm_amd/png_read.py`` only -- importing the package does
-not touch it.  Built in-tree by ``madm_amd/csrc/Makefile``; as with ``_lib.py`` there is no fallback: a missing library or
-symbol raises on import."""
+not touch it.  Built in-tree by ``madm_amd/csrc/Makefile``; as with ``_lib.py`` the binding is read from the header
+(``_cabi.py``) and there is no fallback: a missing library, header or symbol raises on import."""
 import ctypes
 import os
+
+from . import _cabi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MADM_DATA_LIB") or os.path.join(_HERE, "libmadm_data.so")
 
-MDATA_OK, MDATA_ERR_INVALID_ARG, MDATA_ERR_LAUNCH, MDATA_ERR_FORMAT = 0, 1, 2, 3
-MAX_TAPS = 17
-ABI_VERSION = 1
+ABI = _cabi.parse_packaged("madm_data.h")
+_C = ABI.constants
+MDATA_OK, MDATA_ERR_INVALID_ARG = _C["MDATA_OK"], _C["MDATA_ERR_INVALID_ARG"]
+MDATA_ERR_LAUNCH, MDATA_ERR_FORMAT = _C["MDATA_ERR_LAUNCH"], _C["MDATA_ERR_FORMAT"]
+MAX_TAPS = _C["MDATA_MAX_TAPS"]
+ABI_VERSION = 1           # what mdata_abi_version() returns: the header states it in a comment, not in a #define
 
-c_void_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_size_t = ctypes.c_size_t
-
-# every symbol include/madm_data.h declares: (name, restype, argtypes)
-SYMBOLS = [
-    ("mdata_abi_version", c_int, []),
-    ("mdata_last_error", ctypes.c_char_p, []),
-    ("mdata_prep_image_u8", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
-    ("mdata_prep_label_u8", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                    c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    ("mdata_png_unfilter", c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_size_t, c_int]),
-]
+SYMBOLS = ABI.symbols()   # every symbol include/madm_data.h declares: (name, restype, argtypes)
 
 
 class MadmDataError(RuntimeError):

@@ -177,13 +177,15 @@ def test_unfilter_native_status_and_containment():
 
 
 def test_data_header_keeps_out_of_the_main_abi():
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "include", "madm_data.h")).read()
-    assert not re.search(r"madm_[a-z0-9_]+\(", text)
-    from madm_amd import _lib_data
-    declared = set(re.findall(r"\b(mdata_[a-z0-9_]+)\(", text))
+    import ctypes
+    from madm_amd import _cabi, _lib_data
+    abi = _cabi.parse_packaged("madm_data.h")
+    declared = {n for n, _r, _p in abi.prototypes}
+    assert len(declared) == 5 and all(n.startswith("mdata_") for n in declared)        # no madm_* function,
+    assert all(n.startswith("MDATA_") for n in abi.constants) and not abi.structs       # constant or struct
     assert declared == {n for n, _r, _a in _lib_data.SYMBOLS}
+    built = ctypes.CDLL(_lib_data.LIB_PATH)
+    assert all(hasattr(built, n) for n in declared) and not hasattr(built, "madm_abi_version")
     import madm_amd
     assert "_lib_data" not in open(madm_amd.__file__).read()        # package import does not load the second library
 

@@ -13,32 +13,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol():
-    from madm_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "madm_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(madm_[a-z0-9_]+)\s*\(", hdr))
-    assert len(declared) >= 20
+    from madm_amd import _cabi, _lib
+    declared = {name for name, _r, _p in _cabi.parse(os.path.join(ROOT, "include", "madm_hip.h")).prototypes}
+    assert len(declared) >= 20 and all(name.startswith("madm_") for name in declared)
     bound = {name for name, _, _ in _lib.SYMBOLS}
     assert declared == bound, (declared ^ bound)
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
     assert _lib.lib.madm_abi_version() == 6
-
-
-def test_struct_layout_matches_header_field_order():
-    from madm_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "madm_hip.h")).read()
-    body = hdr[hdr.index("typedef struct {", hdr.index("madm_conv2d_fwd: implicit")):hdr.index("} madm_conv2d_args;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.replace("typedef struct {", "").strip()
-        if not decl:
-            continue
-        names = [re.sub(r"[\*\s]", "", n.split()[-1]) for n in decl.split(",")]
-        fields.extend(names)
-    assert fields == [f[0] for f in _lib.Conv2dArgs._fields_], fields
 
 
 def test_argument_validation_reports_errors_without_gpu():
@@ -65,27 +48,6 @@ def test_argument_validation_reports_errors_without_gpu():
     assert lib.madm_attention_fwd(ctypes.byref(at), None) == -2 and b"not instantiated" in lib.madm_last_error()
     assert lib.madm_layernorm_fwd(1, None, None, 1, 8, None, None, 1e-5, None) == -1
     assert lib.madm_groupnorm_stats(0, p, 1, 1, 6, p, None) == -1     # C not a multiple of 4
-
-
-def _header_struct_fields(struct_name):
-    hdr = open(os.path.join(ROOT, "include", "madm_hip.h")).read()
-    end = hdr.index("} " + struct_name + ";")
-    body = hdr[hdr.rindex("typedef struct {", 0, end):end]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.replace("typedef struct {", "").strip()
-        if decl:
-            fields.extend(re.sub(r"[\*\s]", "", n.split()[-1]) for n in decl.split(","))
-    return fields
-
-
-def test_gradient_struct_layouts_match_header():
-    from madm_amd import _lib
-    assert _header_struct_fields("madm_conv2d_wgrad_args") == [f[0] for f in _lib.Conv2dWgradArgs._fields_]
-    assert _header_struct_fields("madm_attention_bwd_args") == [f[0] for f in _lib.AttentionBwdArgs._fields_]
-    assert _header_struct_fields("madm_attention_args") == [f[0] for f in _lib.AttentionArgs._fields_]
-    assert _header_struct_fields("madm_conv2d_plan") == [f[0] for f in _lib.Conv2dPlan._fields_]
 
 
 def test_gradient_entry_points_validate_arguments_without_gpu():
@@ -537,9 +499,9 @@ def test_conv_plans_replay_the_recorded_decisions():
     import json
     from madm_amd import _lib
     tool = _conv_plan_fixture()
-    assert [f[0] for f in tool.Args._fields_] == [f[0] for f in _lib.Conv2dArgs._fields_]
+    assert tool.Args._fields_ == _lib.Conv2dArgs._fields_ and len(tool.Args._fields_) == 48     # names AND types, from the one header
     assert ctypes.sizeof(tool.Args) == ctypes.sizeof(_lib.Conv2dArgs)
-    assert tool.Plan._fields_ == _lib.Conv2dPlan._fields_
+    assert tool.Plan._fields_ == _lib.Conv2dPlan._fields_ and len(tool.Plan._fields_) == 6
     assert "MADM_TUNED_FILE" not in os.environ
     want = json.load(open(tool.FIXTURE))
     assert len(want["explicit"]) >= 200 and all(len(c) == len(want["fields"]) for c in want["explicit"])

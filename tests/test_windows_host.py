@@ -1,8 +1,5 @@
 """Host tests of the canary helper (tests/window_util.py) -- its negative control: no kernel is made to misbehave, the
 buffers are clobbered by hand on the CPU -- and of the table that says which test covers which entry point."""
-import os
-import re
-
 import pytest
 import torch
 
@@ -82,10 +79,8 @@ def test_flat_buffers_start_their_canary_at_element_n():
 
 
 def _header_symbols():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "include", "madm_hip.h")) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return set(re.findall(r"\b(madm_[a-z0-9_]+)\s*\(", text))
+    from madm_amd import _cabi
+    return {name for name, _restype, _params in _cabi.parse_packaged("madm_hip.h").prototypes}
 
 
 def test_every_entry_point_is_covered_by_a_window_test_or_exempt_with_a_reason():

@@ -34,22 +34,21 @@ import struct
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "conv_plans.json")
-c_int, c_void_p, c_float, c_size_t = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_size_t
+c_int, c_size_t = ctypes.c_int, ctypes.c_size_t
 
 
-class Args(ctypes.Structure):   # madm_conv2d_args (tests/test_host.py holds it against madm_amd._lib.Conv2dArgs)
-    _fields_ = [(n, c_void_p if n in ("in1", "in2", "w", "bias", "rowvec", "residual", "out", "stats", "gn_sums1", "gn_sums2",
-                                      "gn_gamma", "gn_beta", "workspace", "ln_colsum", "pn_gamma", "pn_beta")
-                 else c_float if n in ("gn_eps", "ln_eps", "pn_eps") else c_size_t if n == "workspace_bytes" else c_int)
-                for n in ("dtype in1 in2 C1 C2 ld1 ld2 B IH IW OH OW KH KW stride pad_t pad_l upsample w ldw N bias rowvec ldrv "
-                          "residual ldr out ldo out_f32 epilogue stats gn_sums1 gn_sums2 gn_gamma gn_beta gn_groups gn_eps gn_act "
-                          "splitk workspace workspace_bytes ln_colsum ln_eps pn_gamma pn_beta pn_groups pn_eps pn_act").split()]
+def _header_structs():
+    """madm_conv2d_args / madm_conv2d_plan as include/madm_hip.h declares them.  madm_amd/_cabi.py is loaded by path: importing the
+    package would load ITS library, and this tool opens the one it is given."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_cabi", os.path.join(ROOT, "madm_amd", "_cabi.py"))
+    cabi = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cabi)
+    abi = cabi.parse_packaged("madm_hip.h")
+    return abi.struct("madm_conv2d_args"), abi.struct("madm_conv2d_plan")
 
 
-class Plan(ctypes.Structure):   # madm_conv2d_plan
-    _fields_ = [("tile", c_int), ("splitk", c_int), ("splitk_eff", c_int), ("post_gn", c_int), ("tuned_row", c_int),
-                ("workspace_bytes", c_size_t)]
-
+Args, Plan = _header_structs()
 
 PTR = 64                                  # stands for "a tensor is given": the decision never looks behind a pointer
 OVERRIDES = (0, -1, 12, 13, 1)
