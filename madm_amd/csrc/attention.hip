@@ -313,15 +313,26 @@ __global__ __launch_bounds__(NW * 64, NQ > 1 ? 2 : 1) void attn_kernel(const Att
             }
             // row maximum over the four lane groups of a query: v_permlane16/32_swap (VALU) instead of two ds_bpermute round
             // trips -- this exchange sits on the critical path of every KV tile (the exponentials wait for it)
+            // Inline asm, not __builtin_amdgcn_permlane16/32_swap(x, x): with the SAME value as both operands hipcc hands back
+            // the first result for both, the fmaxf of the two folds away, and every lane ends up with lane group 0's maximum
+            // (keys 0..3 of each 16-key sub-tile) instead of the row's.  That is still one reference for the whole row, so random
+            // inputs pass, but a key outside lane group 0 that leads group 0's best by 88 nats (11 in f16) overflowed P: NaN rows.
+            // Now both are computed: mx0 = lane group 0's maximum (the reference this kernel has always used, kept so that
+            // results stay bit for bit where it was sound) and mx = the row's true maximum; the reference is raised to within
+            // 8 binades of the true maximum, so P <= 256 in every type.  s_nop: the swap's two wait states after the VALU
+            // write of its operands and one before the VALU read of its results.
+            float mx0 = mx;
             {
-                const unsigned xi = __builtin_bit_cast(unsigned, mx);
-                const auto r16 = __builtin_amdgcn_permlane16_swap(xi, xi, false, false);
-                mx = fmaxf(__builtin_bit_cast(float, r16[0]), __builtin_bit_cast(float, r16[1]));
-                const unsigned yi = __builtin_bit_cast(unsigned, mx);
-                const auto r32 = __builtin_amdgcn_permlane32_swap(yi, yi, false, false);
-                mx = fmaxf(__builtin_bit_cast(float, r32[0]), __builtin_bit_cast(float, r32[1]));
+#if defined(__HIP_DEVICE_COMPILE__)
+                float g0 = mx, t0 = mx, g1, t1;
+                asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 0\n\tv_max_f32 %2, %0, %1" : "+v"(g0), "+v"(t0), "=&v"(mx));
+                g1 = g0; t1 = mx;
+                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(g0), "+v"(g1));
+                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0\n\tv_max_f32 %0, %0, %1" : "+v"(mx), "+v"(t1));
+                mx0 = g0;
+#endif
             }
-            const float m_new = fmaxf(m_run[g], mx * p.scale_log2);
+            const float m_new = fmaxf(m_run[g], fmaxf(mx0 * p.scale_log2, mx * p.scale_log2 - 8.0f));
             const float alpha = __builtin_amdgcn_exp2f(m_run[g] - m_new);
             m_run[g] = m_new;
             const float nm = -m_new;
