@@ -1,5 +1,5 @@
-"""Reader of the two C ABI headers (include/madm_hip.h, include/madm_data.h): the ctypes structures, signatures and
-constants that ``_lib.py`` / ``_lib_data.py`` bind come from the text every ``.hip`` file is compiled against, not from a
+"""Reader of the C ABI headers (include/madm_hip.h, include/madm_data.h, include/madm_det.h): the ctypes structures, signatures
+and constants that ``_lib.py`` / ``_lib_data.py`` / ``_lib_det.py`` bind come from the text every ``.hip`` file is compiled against, not from a
 table kept next to it.  Standard library only: no torch, no library is loaded (tools/conv_plan_fixture.py and the host
 tests use it on their own).
 

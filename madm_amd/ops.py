@@ -189,6 +189,53 @@ class _Prof:
         return False
 
 
+# ---- deterministic mode -------------------------------------------------------------------------------------------------------
+# A plain process-wide flag (NOT thread-local: the backward runs on the autograd thread and must see it).  While it is set, the
+# seven reductions whose f32 additions the main library orders by scheduling take a fixed order instead: colsum,
+# groupnorm_stats, groupnorm_backward (sums and dgamma / dbeta), layernorm_backward (dgamma / dbeta) and dwconv3x3_wgrad go to
+# libmadm_det.so (include/madm_det.h; loaded by the first switch into the mode, never by importing the package), and
+# conv2d_wgrad runs with one pixel slice (a sole owner per dw tile).  DESIGN.md section 24 has the site table, what is left as
+# it is (f64 accumulation of f32 block partials) and what the mode costs.  With more than one rank the mode fixes each
+# rank's own arithmetic; the order inside the gradient all-reduce is the collective library's.
+_DETERMINISTIC = False
+_det = None
+
+
+def set_deterministic(flag):
+    """Switches the fixed-order gradient reductions on or off for the whole process; returns the previous value."""
+    global _DETERMINISTIC, _det
+    if flag and _det is None:
+        from . import _lib_det
+        _det = _lib_det
+    prev, _DETERMINISTIC = _DETERMINISTIC, bool(flag)
+    return prev
+
+
+def is_deterministic():
+    return _DETERMINISTIC
+
+
+class deterministic:
+    """``with ops.deterministic():`` -- the mode for a block, the previous value restored on exit (also on an exception)."""
+
+    def __init__(self, flag=True):
+        self.flag = flag
+
+    def __enter__(self):
+        self.prev = set_deterministic(self.flag)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.prev)
+        return False
+
+
+def _det_workspace(query, *shape, device):
+    """(pointer, bytes) of the per-stream workspace, at least what the library's host query asks for these shapes"""
+    ws = _workspace(int(query(*shape)), device)
+    return ctypes.c_void_p(ws.data_ptr()), ws.numel()
+
+
 def _workspace(nbytes, device):
     key = (device.index, torch.cuda.current_stream().cuda_stream)
     ws = _workspaces.get(key)
@@ -363,7 +410,7 @@ def conv2d_wgrad(x1, dout, B, IH, IW, *, x2=None, KH=1, KW=1, stride=1, pad_t=0,
     a.KH, a.KW, a.stride, a.pad_t, a.pad_l = KH, KW, stride, pad_t, pad_l
     a.upsample = 1 if upsample else 0
     a.N = N
-    a.splitm = int(splitm)
+    a.splitm = 1 if _DETERMINISTIC else int(splitm)   # one pixel slice: a sole owner per dw tile, one add per dbias address
     if dbias is not None:
         _need_cuda(dbias)
         assert dbias.dtype == torch.float32 and dbias.is_contiguous() and dbias.numel() == N
@@ -474,6 +521,11 @@ def colsum(x, B, HW, out=None):
     if out is None:
         out = zeros_f32((B, x.shape[1]), x.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, x.shape[1])
+    if _DETERMINISTIC:
+        ws, nws = _det_workspace(_det.lib.mdet_colsum_workspace_bytes, B, HW, x.shape[1], device=x.device)
+        _det.check(_det.lib.mdet_colsum(dtype_code(x), x.data_ptr(), x.stride(0), B, HW, x.shape[1], out.data_ptr(), ws, nws,
+                                        _stream()), "mdet_colsum")
+        return out
     check(lib.madm_colsum(dtype_code(x), x.data_ptr(), x.stride(0), B, HW, x.shape[1], out.data_ptr(), _stream()),
           "madm_colsum")
     return out
@@ -564,6 +616,11 @@ def groupnorm_stats(x, B, HW, chsums):
     _need_cuda(x, chsums)
     assert x.is_contiguous() and x.shape[0] == B * HW
     assert chsums.dtype == torch.float64 and chsums.is_contiguous() and chsums.numel() == B * x.shape[1] * 2
+    if _DETERMINISTIC:
+        ws, nws = _det_workspace(_det.lib.mdet_groupnorm_stats_workspace_bytes, B, HW, x.shape[1], device=x.device)
+        _det.check(_det.lib.mdet_groupnorm_stats(dtype_code(x), x.data_ptr(), B, HW, x.shape[1], chsums.data_ptr(), ws, nws,
+                                                 _stream()), "mdet_groupnorm_stats")
+        return
     check(lib.madm_groupnorm_stats(dtype_code(x), x.data_ptr(), B, HW, x.shape[1], chsums.data_ptr(), _stream()),
           "madm_groupnorm_stats")
 
@@ -640,17 +697,28 @@ def groupnorm_backward(xs, dy, B, HW, G, gamma, beta, eps, stats, act=None, dgam
     off = 0
     for x in xs:
         assert x.is_contiguous() and x.shape[0] == B * HW
-        check(lib.madm_groupnorm_bwd_sums(dtype_code(x), x.data_ptr(), dy.data_ptr(), dy.stride(0), B, HW, x.shape[1],
-                                          off, Ctot, G, stats[0].data_ptr(), C1, s2, gamma.data_ptr(), beta.data_ptr(),
-                                          float(eps), code, bsums.data_ptr(), _stream()), "madm_groupnorm_bwd_sums")
+        if _DETERMINISTIC:
+            ws, nws = _det_workspace(_det.lib.mdet_groupnorm_bwd_sums_workspace_bytes, B, HW, x.shape[1], device=dev)
+            _det.check(_det.lib.mdet_groupnorm_bwd_sums(dtype_code(x), x.data_ptr(), dy.data_ptr(), dy.stride(0), B, HW,
+                                                        x.shape[1], off, Ctot, G, stats[0].data_ptr(), C1, s2,
+                                                        gamma.data_ptr(), beta.data_ptr(), float(eps), code,
+                                                        bsums.data_ptr(), ws, nws, _stream()), "mdet_groupnorm_bwd_sums")
+        else:
+            check(lib.madm_groupnorm_bwd_sums(dtype_code(x), x.data_ptr(), dy.data_ptr(), dy.stride(0), B, HW, x.shape[1],
+                                              off, Ctot, G, stats[0].data_ptr(), C1, s2, gamma.data_ptr(), beta.data_ptr(),
+                                              float(eps), code, bsums.data_ptr(), _stream()), "madm_groupnorm_bwd_sums")
         off += x.shape[1]
+    if _DETERMINISTIC:   # the images of bsums in index order, one update per channel; the apply kernel gets no dgamma / dbeta
+        _det.check(_det.lib.mdet_groupnorm_bwd_params(bsums.data_ptr(), B, Ctot, dgamma.data_ptr(), dbeta.data_ptr(),
+                                                      _stream()), "mdet_groupnorm_bwd_params")
+    pg, pb = (None, None) if _DETERMINISTIC else (dgamma.data_ptr(), dbeta.data_ptr())
     dxs, off = [], 0
     for x in xs:
         dx = torch.empty_like(x)
         check(lib.madm_groupnorm_bwd_apply(dtype_code(x), x.data_ptr(), dy.data_ptr(), dy.stride(0), dx.data_ptr(), B, HW,
                                            x.shape[1], off, Ctot, G, stats[0].data_ptr(), C1, s2, gamma.data_ptr(),
-                                           beta.data_ptr(), float(eps), code, bsums.data_ptr(), dgamma.data_ptr(),
-                                           dbeta.data_ptr(), _ptr(dres), dres.stride(0) if dres is not None else 0,
+                                           beta.data_ptr(), float(eps), code, bsums.data_ptr(), pg,
+                                           pb, _ptr(dres), dres.stride(0) if dres is not None else 0,
                                            _stream()), "madm_groupnorm_bwd_apply")
         dxs.append(dx)
         off += x.shape[1]
@@ -667,9 +735,17 @@ def layernorm_backward(x, dy, gamma, eps, dgamma=None, dbeta=None, dres=None):
         dgamma = zeros_f32((x.shape[1],), x.device)
         dbeta = zeros_f32((x.shape[1],), x.device)
     dx = torch.empty_like(x)
+    det = _DETERMINISTIC     # dx from the main library's kernel without its parameter sums; those in a fixed order behind it
     check(lib.madm_layernorm_bwd(dtype_code(x), x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.shape[0], x.shape[1],
-                                 gamma.data_ptr(), float(eps), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dres), _stream()),
+                                 gamma.data_ptr(), float(eps), None if det else dgamma.data_ptr(),
+                                 None if det else dbeta.data_ptr(), _ptr(dres), _stream()),
           "madm_layernorm_bwd")
+    if det:
+        M, C = x.shape
+        ws, nws = _det_workspace(_det.lib.mdet_layernorm_bwd_params_workspace_bytes, M, C, device=x.device)
+        _det.check(_det.lib.mdet_layernorm_bwd_params(dtype_code(x), x.data_ptr(), dy.data_ptr(), M, C, float(eps),
+                                                      dgamma.data_ptr(), dbeta.data_ptr(), ws, nws, _stream()),
+                   "mdet_layernorm_bwd_params")
     return dx, dgamma, dbeta
 
 
@@ -1120,6 +1196,11 @@ def dwconv3x3_wgrad(x, dy, B, H, W, dilation, dw=None):
     if dw is None:
         dw = zeros_f32((9, C), x.device)
     assert dw.dtype == torch.float32 and dw.is_contiguous() and tuple(dw.shape) == (9, C)
+    if _DETERMINISTIC:
+        ws, nws = _det_workspace(_det.lib.mdet_dwconv3x3_wgrad_workspace_bytes, B, H, W, C, device=x.device)
+        _det.check(_det.lib.mdet_dwconv3x3_wgrad(dtype_code(x), x.data_ptr(), dy.data_ptr(), dy.stride(0), dw.data_ptr(), B, H,
+                                                 W, C, int(dilation), ws, nws, _stream()), "mdet_dwconv3x3_wgrad")
+        return dw
     check(lib.madm_dwconv3x3_wgrad(dtype_code(x), x.data_ptr(), dy.data_ptr(), dy.stride(0), dw.data_ptr(), B, H, W, C,
                                    int(dilation), _stream()), "madm_dwconv3x3_wgrad")
     return dw

@@ -13,7 +13,7 @@
 """
 import torch
 
-from . import optim
+from . import ops, optim
 from .dist import GradBucketReducer
 
 
@@ -23,8 +23,9 @@ class MadmTrainer:
 
     def __init__(self, model, lr, weight_decay, grad_clip=None, unet_lr=None, betas=(0.9, 0.999), eps=1e-8, dist=None,
                  amp=True, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000,
-                 lr_multiplier=None, exchange="allreduce", wire_dtype=None):
+                 lr_multiplier=None, exchange="allreduce", wire_dtype=None, deterministic=False):
         self.model = model
+        self.deterministic = bool(deterministic)   # run_step under ops.deterministic(): see that docstring
         try:      # the extractor whose per-pass range assert this trainer defers to the end of its step
             self._ldm = model.backbone.feature_extractor.ldm_extractor
         except AttributeError:
@@ -132,7 +133,17 @@ class MadmTrainer:
         self.flush()
 
     def run_step(self, data):
-        """Returns (loss dict of python floats, total gradient norm, stepped)."""
+        """Returns (loss dict of python floats, total gradient norm, stepped).  With ``deterministic=True`` the whole step
+        (forward, backward, optimizer) runs in ``ops.deterministic()`` mode -- every f32 accumulation of this rank's step in
+        a fixed order, so that two runs from the same state give the same bits -- and the previous value of the switch is
+        restored afterwards, also when the step raises.  With more than one rank this fixes each rank's own arithmetic; the
+        order inside the gradient all-reduce is the collective library's."""
+        if not self.deterministic:
+            return self._run_step(data)
+        with ops.deterministic():
+            return self._run_step(data)
+
+    def _run_step(self, data):
         model = self.model
         assert model.training, "[MadmTrainer] model was changed to eval mode!"
         self.opt.zero_grad()
