@@ -393,6 +393,16 @@ int madm_confusion_matrix(const int64_t* pred, const int64_t* gt, size_t n, int 
  * mmcv DepthwiseSeparableConvModule.depthwise_conv of the sep-ASPP (daformer_head.py:383-398). */
 int madm_dwconv3x3(int dtype, const void* x, const float* w, const float* scale, const float* shift, void* y,
                    int ldy, int B, int H, int W, int C, int dilation, int act, void* stream);
+/* Host planner (no reference counterpart; additive to ABI 6): the kernel variant, tile and grid that madm_dwconv3x3
+ * (wgrad = 0) or madm_dwconv3x3_wgrad (wgrad = 1) launches for this geometry -- both launchers call it, so what it
+ * returns is what runs.  It reads MADM_DWCONV_KERNEL on every call like they do (0 / unset = choose, 1 = plain, 2 = comb,
+ * 3 = comb with per-XCD channel slabs, 4 = lattice; a forced variant the geometry does not admit falls back as the
+ * launch does).  out = six ints {variant, ny, nx, th, tw, blocks}:
+ *   variant 4 (lattice): ny x nx tiles of th x tw lattice pixels (at most 15 x 15) per residue class of the dilation;
+ *   variants 2 / 3 (comb, forward only): nx = blocks of tw = 4 outputs per residue class and row, ny = th = 0;
+ *   variant 1 (plain): ny = th = tw = 0; nx = 0 (forward) or the pixels per workgroup (weight gradient);
+ *   blocks = workgroups of the launch.  Touches no device memory. */
+int madm_dwconv3x3_plan(int dtype, int B, int H, int W, int C, int dilation, int* out, int wgrad);
 /* out[r][i] = tanh(a1[i]) x1[i] + tanh(a2[i]) x2[i] for r < repeat (a1/a2 NULL = gate 1, x2 NULL = one term):
  * ClipFeatureProject.get_cond_prompt / get_cond_time + the batch repeat_interleave
  * (modeling/meta_arch/ldm_base.py:675-712,915-917). */

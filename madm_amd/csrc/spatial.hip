@@ -425,37 +425,46 @@ int madm_resize_bilinear_nchw_f32(const float* in, float* out, int planes, int I
     return madm_check_launch("resize_bilinear_nchw_kernel");
 }
 
-int madm_dwconv3x3(int dtype, const void* x, const float* w, const float* scale, const float* shift, void* y, int ldy,
-                   int B, int H, int W, int C, int dilation, int act, void* stream) {
-    MADM_REQUIRE(x && w && scale && shift && y && B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "dwconv3x3: bad args");
-    MADM_REQUIRE(madm_aligned16(x, y), "dwconv3x3: x / y must be 16-byte aligned (16-byte chunks)");
-    MADM_REQUIRE(madm_aligned16(w, scale, shift), "dwconv3x3: w / scale / shift must be 16-byte aligned (read as float4)");
+// Which kernel a depthwise launch takes, and its tile and grid: the ONE place where the variant predicates and the tile
+// arithmetic live (madm_dwconv3x3 and madm_dwconv3x3_wgrad both launch what this returns; include/madm_hip.h states `out`).
+// MADM_DWCONV_KERNEL (tests, A/B runs), read on every call: 0 / unset = choose, 1 = plain, 2 = comb, 3 = comb with per-XCD
+// channel slabs, 4 = lattice; the weight gradient has the plain and the lattice kernel only (4 forces the lattice one,
+// every other non-zero value forbids it).
+int madm_dwconv3x3_plan(int dtype, int B, int H, int W, int C, int dilation, int* out, int wgrad) {
+    const char* who = wgrad ? "dwconv3x3_wgrad" : "dwconv3x3";
+    MADM_REQUIRE(out && B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "%s: bad plan argument", who);
+    MADM_REQUIRE(madm_dtype_ok(dtype), "unknown dtype %d", dtype);
     const int epc = madm_epc(dtype);
-    MADM_REQUIRE(C % epc == 0 && ldy >= C && ldy % epc == 0 && act >= 0 && act <= 2, "dwconv3x3: bad C/ldy/act");
+    MADM_REQUIRE(C % epc == 0, "%s: C must be a multiple of %d", who, epc);
     const size_t total = (size_t)B * H * W * (C / epc);
-    MADM_REQUIRE(total < 0x7fffffffull, "dwconv3x3: tensor too large for 32-bit indexing");
-    hipStream_t s = (hipStream_t)stream;
-    // MADM_DWCONV_KERNEL (tests, A/B runs): 0 / unset = choose, 1 = plain, 2 = comb, 3 = comb with per-XCD channel slabs, 4 = lattice
+    MADM_REQUIRE(wgrad || total < 0x7fffffffull, "dwconv3x3: tensor too large for 32-bit indexing");
     const char* fe = getenv("MADM_DWCONV_KERNEL");
     const int force = fe ? atoi(fe) : 0;
+    int variant = 1, ny = 0, nx = 0, th = 0, tw = 0;
+    size_t blocks = 0;
     // 4 = the lattice kernel (one residue class of the dilation per workgroup, halo in LDS): large maps with whole
-    // 128-byte channel slabs
-    {
-        const int chs = 8 * epc;
-        const int shmax = (H + dilation - 1) / dilation, swmax = (W + dilation - 1) / dilation;
-        const bool fits = C % chs == 0 && dilation > 1;
-        const bool pays = total >= ((size_t)1 << 21) && shmax >= 8 && swmax >= 8;
-        if (fits && (force == 4 || (force == 0 && pays))) {
-            const int ny = (shmax + 14) / 15, nx = (swmax + 14) / 15;
-            const int th = (shmax + ny - 1) / ny, tw = (swmax + nx - 1) / nx;
-            const size_t blocks = (size_t)B * dilation * dilation * ny * nx * (C / chs);
-            MADM_REQUIRE(blocks < 0x7fffffffull, "dwconv3x3: grid too large");
-            MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_lattice_kernel<T><<<(unsigned)blocks, 256, 0, s>>>(
-                                           (const T*)x, w, scale, shift, (T*)y, ldy, B, H, W, C, dilation, act, ny, nx, th, tw)));
-            return madm_check_launch("dwconv3x3_lattice_kernel");
-        }
-    }
-    if (force != 1 && W >= 4 * dilation) {
+    // 128-byte channel slabs, cut into tiles of at most 15 x 15 lattice pixels
+    const int chs = 8 * epc;
+    const int shmax = (H + dilation - 1) / dilation, swmax = (W + dilation - 1) / dilation;
+    const int lny = (shmax + 14) / 15, lnx = (swmax + 14) / 15;
+    const bool fits = C % chs == 0 && dilation > 1;
+    // the weight gradient's workgroup walks the ny * nx tiles of its class one after the other (load, barrier, multiply):
+    // with few tiles per class nothing covers the loads -- head tensor, 2 x 512 x 512 x 1024: 1 415 -> 709 us at dilation 6
+    // (36 tiles), 1 355 -> 905 at 12 (9), 1 388 -> 1 461 at 18 (4)
+    const bool pays = total >= ((size_t)1 << 21) && (wgrad ? lny * lnx >= 9 : (shmax >= 8 && swmax >= 8));
+    if (fits && (force == 4 || (force == 0 && pays))) {
+        variant = 4;
+        ny = lny; nx = lnx;
+        th = (shmax + ny - 1) / ny; tw = (swmax + nx - 1) / nx;
+        blocks = (size_t)B * dilation * dilation * (C / chs) * (wgrad ? 1 : (size_t)ny * nx);
+        MADM_REQUIRE(blocks < 0x7fffffffull, "%s: grid too large", who);
+    } else if (wgrad) {
+        const size_t npix = (size_t)B * H * W;
+        size_t ppb = (npix + 2047) / 2048;                               // pixels per workgroup
+        if (ppb < 64) ppb = 64;
+        nx = (int)ppb;
+        blocks = (npix + ppb - 1) / ppb;
+    } else if (force != 1 && W >= 4 * dilation) {
         constexpr int PX = 4;
         const int kmax = (W + dilation - 1) / dilation;                  // outputs per residue class (upper bound)
         const int kblocks = (kmax + PX - 1) / PX;
@@ -463,19 +472,46 @@ int madm_dwconv3x3(int dtype, const void* x, const float* w, const float* scale,
         // slabs of at least 128 B per pixel, and enough work for eight workgroups per CU
         const bool slabs = (C / epc) % 8 == 0 &&
                            (force == 3 || (force == 0 && C / 8 * madm_esize(dtype) >= 128 && tot >= ((size_t)1 << 19)));
-        if (slabs) {
-            const unsigned g = (grid_for(tot, 65536) + 7u) & ~7u;
-            MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_comb_kernel<T, PX, true><<<g, 256, 0, s>>>(
-                                           (const T*)x, w, scale, shift, (T*)y, ldy, B, H, W, C, dilation, act, kblocks)));
-        } else {
-            MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_comb_kernel<T, PX, false><<<grid_for(tot, 65536), 256, 0, s>>>(
-                                           (const T*)x, w, scale, shift, (T*)y, ldy, B, H, W, C, dilation, act, kblocks)));
-        }
-        return madm_check_launch("dwconv3x3_comb_kernel");
+        variant = slabs ? 3 : 2;
+        nx = kblocks; tw = PX;
+        blocks = slabs ? ((grid_for(tot, 65536) + 7u) & ~7u) : grid_for(tot, 65536);
+    } else {
+        blocks = grid_for(total, 16384);
     }
-    MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_kernel<T><<<grid_for(total, 16384), 256, 0, s>>>((const T*)x, w, scale, shift, (T*)y,
-                                                                                        ldy, B, H, W, C, dilation, act)));
-    return madm_check_launch("dwconv3x3_kernel");
+    out[0] = variant; out[1] = ny; out[2] = nx; out[3] = th; out[4] = tw; out[5] = (int)blocks;
+    return MADM_OK;
+}
+
+int madm_dwconv3x3(int dtype, const void* x, const float* w, const float* scale, const float* shift, void* y, int ldy,
+                   int B, int H, int W, int C, int dilation, int act, void* stream) {
+    MADM_REQUIRE(x && w && scale && shift && y && B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "dwconv3x3: bad args");
+    MADM_REQUIRE(madm_aligned16(x, y), "dwconv3x3: x / y must be 16-byte aligned (16-byte chunks)");
+    MADM_REQUIRE(madm_aligned16(w, scale, shift), "dwconv3x3: w / scale / shift must be 16-byte aligned (read as float4)");
+    const int epc = madm_epc(dtype);
+    MADM_REQUIRE(C % epc == 0 && ldy >= C && ldy % epc == 0 && act >= 0 && act <= 2, "dwconv3x3: bad C/ldy/act");
+    int p[6];
+    if (const int rc = madm_dwconv3x3_plan(dtype, B, H, W, C, dilation, p, 0)) return rc;
+    const int ny = p[1], nx = p[2], th = p[3], tw = p[4];
+    const unsigned blocks = (unsigned)p[5];
+    hipStream_t s = (hipStream_t)stream;
+    switch (p[0]) {
+    case 4:
+        MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_lattice_kernel<T><<<blocks, 256, 0, s>>>(
+                                       (const T*)x, w, scale, shift, (T*)y, ldy, B, H, W, C, dilation, act, ny, nx, th, tw)));
+        return madm_check_launch("dwconv3x3_lattice_kernel");
+    case 3:
+        MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_comb_kernel<T, 4, true><<<blocks, 256, 0, s>>>(
+                                       (const T*)x, w, scale, shift, (T*)y, ldy, B, H, W, C, dilation, act, nx)));
+        return madm_check_launch("dwconv3x3_comb_kernel");
+    case 2:
+        MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_comb_kernel<T, 4, false><<<blocks, 256, 0, s>>>(
+                                       (const T*)x, w, scale, shift, (T*)y, ldy, B, H, W, C, dilation, act, nx)));
+        return madm_check_launch("dwconv3x3_comb_kernel");
+    default:
+        MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_kernel<T><<<blocks, 256, 0, s>>>((const T*)x, w, scale, shift, (T*)y, ldy, B, H, W,
+                                                                               C, dilation, act)));
+        return madm_check_launch("dwconv3x3_kernel");
+    }
 }
 
 int madm_scale_pad_crop_nchw_f32(const float* in, float* out, int planes, int IH, int IW, int y1, int x1, int OH, int OW,

@@ -636,35 +636,18 @@ int madm_dwconv3x3_wgrad(int dtype, const void* x, const void* dy, int lddy, flo
     MADM_REQUIRE(madm_aligned16(x, dy), "dwconv3x3_wgrad: x / dy must be 16-byte aligned (16-byte chunks)");
     const int epc = madm_epc(dtype);
     MADM_REQUIRE(C % epc == 0 && lddy % epc == 0 && lddy >= C, "dwconv3x3_wgrad: C / lddy must be multiples of %d", epc);
+    int p[6];   // variant, tile and grid: madm_dwconv3x3_plan (spatial.hip), shared with the forward
+    if (const int rc = madm_dwconv3x3_plan(dtype, B, H, W, C, dilation, p, 1)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    {   // large maps with whole 128-byte channel slabs: the lattice kernel (MADM_DWCONV_KERNEL=4 forces it, =1 forbids it)
-        const char* fe = getenv("MADM_DWCONV_KERNEL");
-        const int force = fe ? atoi(fe) : 0;
-        const int chs = 8 * epc;
-        const int shmax = (H + dilation - 1) / dilation, swmax = (W + dilation - 1) / dilation;
-        const bool fits = C % chs == 0 && dilation > 1;
-        const int ny = (shmax + 14) / 15, nx = (swmax + 14) / 15;
-        // a workgroup walks the ny * nx tiles of its class one after the other (load, barrier, multiply): with few tiles
-        // per class nothing covers the loads -- head tensor, 2 x 512 x 512 x 1024: 1 415 -> 709 us at dilation 6 (36
-        // tiles), 1 355 -> 905 at 12 (9), 1 388 -> 1 461 at 18 (4)
-        const bool pays = (size_t)B * H * W * (C / epc) >= ((size_t)1 << 21) && ny * nx >= 9;
-        if (fits && (force == 4 || (force == 0 && pays))) {
-            const int th = (shmax + ny - 1) / ny, tw = (swmax + nx - 1) / nx;
-            const size_t blocks = (size_t)B * dilation * dilation * (C / chs);
-            MADM_REQUIRE(blocks < 0x7fffffffull, "dwconv3x3_wgrad: grid too large");
-            MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_wgrad_lattice_kernel<T><<<(unsigned)blocks, 256, 0, s>>>(
-                                           (const T*)x, (const T*)dy, lddy, dw, B, H, W, C, dilation, ny, nx, th, tw)));
-            return madm_check_launch("dwconv3x3_wgrad_lattice_kernel");
-        }
+    if (p[0] == 4) {
+        MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_wgrad_lattice_kernel<T><<<(unsigned)p[5], 256, 0, s>>>(
+                                       (const T*)x, (const T*)dy, lddy, dw, B, H, W, C, dilation, p[1], p[2], p[3], p[4])));
+        return madm_check_launch("dwconv3x3_wgrad_lattice_kernel");
     }
     const size_t shm = (size_t)9 * C * sizeof(float);
     MADM_REQUIRE(shm <= 64 * 1024, "dwconv3x3_wgrad: C = %d too large", C);
-    const size_t npix = (size_t)B * H * W;
-    int ppb = (int)((npix + 2047) / 2048);
-    if (ppb < 64) ppb = 64;
-    const unsigned blocks = (unsigned)((npix + ppb - 1) / ppb);
-    MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_wgrad_kernel<T><<<blocks, 256, shm, s>>>((const T*)x, (const T*)dy, lddy, dw, B, H,
-                                                                                 W, C, dilation, ppb)));
+    MADM_DISPATCH_DTYPE(dtype, (dwconv3x3_wgrad_kernel<T><<<(unsigned)p[5], 256, shm, s>>>((const T*)x, (const T*)dy, lddy, dw, B,
+                                                                                         H, W, C, dilation, p[2])));
     return madm_check_launch("dwconv3x3_wgrad_kernel");
 }
 

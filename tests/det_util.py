@@ -112,7 +112,12 @@ def row_case(family, name, C, two_source=False):
 @functools.lru_cache(maxsize=None)
 def dw_case(name, C):
     _n, B, H, W, dil, _chunks, _s = next(c for c in DW_CASES if c[0] == name)
-    seed = 900 + [c[0] for c in DW_CASES].index(name)
+    return dw_geometry_case(B, H, W, dil, C, 900 + [c[0] for c in DW_CASES].index(name))
+
+
+@functools.lru_cache(maxsize=None)
+def dw_geometry_case(B, H, W, dil, C, seed):
+    """x, dy (integers of magnitude <= 2, tokens [B*H*W, C]) and the term tensor of the depthwise weight gradient at any geometry"""
     ns = SimpleNamespace(family="dwconv3x3_wgrad", B=1, R=B * H * W, C=C, images=B, H=H, W=W, dil=dil)
     x = ints((B, C, H, W), seed, 2)
     dy = ints((B, C, H, W), seed + 50, 2)

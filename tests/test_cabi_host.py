@@ -109,7 +109,7 @@ def test_a_missing_header_is_an_import_error_that_names_the_path():
 
 def test_the_headers_parse_to_the_counts_they_hold():
     a, d = _cabi.parse_packaged("madm_hip.h"), _cabi.parse_packaged("madm_data.h")
-    assert len(a.prototypes) == 82 and len({n for n, _r, _p in a.prototypes}) == 82
+    assert len(a.prototypes) == 83 and len({n for n, _r, _p in a.prototypes}) == 83
     assert {n: len(s._fields_) for n, s in a.structs.items()} == {
         "madm_conv2d_args": 48, "madm_conv2d_plan": 6, "madm_attention_args": 15, "madm_attention_bwd_args": 25,
         "madm_conv2d_wgrad_args": 24, "madm_vis_tile": 7}

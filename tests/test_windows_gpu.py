@@ -1789,6 +1789,7 @@ EXEMPT = {
     "madm_abi_version": "host query, no device memory",
     "madm_last_error": "host query, no device memory",
     "madm_conv2d_make_plan": "host planner: touches no tensor",
+    "madm_dwconv3x3_plan": "host planner: touches no tensor",
     "madm_conv2d_can_fuse_groupnorm": "host predicate: touches no tensor",
     "madm_conv2d_tile_name": "host table lookup, no device memory",
     "madm_set_tuning_profile": "host process state, no device memory",
