@@ -14,6 +14,10 @@ Two modes, selected by ``nn.Module.training`` exactly as torch's BatchNorm2d / D
   running statistics updated with momentum 0.1, ``Dropout2d(0.1)`` as a per-(image, channel) scale.  ``forward_tokens``
   records what :meth:`DAFormerHead.backward_tokens` needs (raw conv outputs + their batch sums; normalised tensors are
   recomputed), the backward returns the feature gradients and ``{parameter name: f32 gradient}``.
+
+``final_fuse_vae_decoder_feat=True`` (daformer_head.py:575-589,689-698,721-723): the scales are fused at
+half of the first feature's size, and that feature joins at full size through ``vae_decoder_feat_proj`` and a classifier over
+both -- one kernel (``ops.upsample_cat_classify``) where no tape is kept and the geometry is an exact 2x.
 """
 import torch
 import torch.nn as nn
@@ -21,7 +25,7 @@ import torch.nn as nn
 from . import ops, packing
 from ._lib import EPI_RELU, EPI_NONE, ACT_RELU, ACT_NONE
 from .nn import Tok, Linear, _Packed
-from .backbone import widen_tokens
+from .backbone import widen_tokens, BottleneckBlock, _D2Conv
 
 
 class _BN(nn.Module):
@@ -224,20 +228,87 @@ class ASPPWrapper(nn.Module):
         return dx
 
 
+class NarrowBottleneckBlock(nn.Module):
+    """detectron2 ``BottleneckBlock(norm="GN")`` whose bottleneck is narrower than a K-tile of the conv kernels (the flagged
+    head's 128 -> 32 -> 64, daformer_head.py:576-588).  The parameters have the reference's names and shapes; the arithmetic
+    runs through :class:`backbone.BottleneckBlock` on a block whose bottleneck is zero-padded to the K-tile: the padding
+    channels carry zero weights, a GroupNorm group of their own (same channels per group as the real ones) and gamma =
+    beta = 0, so they are 0 everywhere, add nothing to a real channel's sums and take no gradient.  The padded twin is derived
+    data like a packed weight: rebuilt when a parameter's version or storage moves, kept out of ``state_dict()``."""
+    PAD = 64
+
+    def __init__(self, in_channels, out_channels, *, bottleneck_channels, norm="GN"):
+        super().__init__()
+        assert norm == "GN" and in_channels != out_channels and out_channels % self.PAD == 0 and bottleneck_channels % 32 == 0
+        self.in_channels, self.out_channels, self.bottleneck_channels = in_channels, out_channels, bottleneck_channels
+        self.shortcut = _D2Conv(in_channels, out_channels, 1)
+        self.conv1 = _D2Conv(in_channels, bottleneck_channels, 1)
+        self.conv2 = _D2Conv(bottleneck_channels, bottleneck_channels, 3, padding=1)
+        self.conv3 = _D2Conv(bottleneck_channels, out_channels, 1)
+
+    def _wide(self):
+        real = dict(self.named_parameters())
+        key = tuple((p._version, p.data_ptr()) for p in real.values())
+        c = self.__dict__.get("_wide_cache")
+        if c is not None and c[0] == key:
+            return c[1]
+        bc = self.bottleneck_channels
+        bw = packing.round_up(bc, self.PAD)
+        dev = self.conv1.weight.device
+        wide = c[1] if c is not None and c[1].conv1.weight.device == dev else None
+        if wide is None:
+            wide = BottleneckBlock(self.in_channels, self.out_channels, bottleneck_channels=bw).to(dev)
+            for conv in (wide.conv1, wide.conv2):      # one group per bc / 32 channels, padding included
+                conv.norm.num_groups = bw // (bc // 32)
+            for p in wide.parameters():
+                p.requires_grad_(False)
+        with torch.no_grad():
+            for name, p in wide.named_parameters():
+                r = real[name]
+                p.zero_()
+                p[tuple(slice(0, s) for s in r.shape)].copy_(r.detach())
+        ops.note_build()
+        self.__dict__["_wide_cache"] = (key, wide)
+        return wide
+
+    def forward(self, x, tape=None):
+        return self._wide().forward(x, tape=tape)
+
+    def backward(self, rec, dout, need_dx=True):
+        """As ``BottleneckBlock.backward``; the gradients come back in the parameters' own shapes."""
+        dx, g = rec[0].backward(rec, dout, need_dx=need_dx)
+        real = dict(self.named_parameters())
+        return dx, {k: v[tuple(slice(0, s) for s in real[k].shape)] for k, v in g.items()}
+
+    def __deepcopy__(self, memo):   # the padded twin is derived data: copies (the EMA teacher) rebuild their own
+        import copy
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k != "_wide_cache":
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        return new
+
+
 class DAFormerHead(nn.Module):
+    FUSE_PROJ_CHANNELS = 64   # vae_decoder_feat_proj: BottleneckBlock(128 -> 64, bottleneck 32), daformer_head.py:576-589
+    # final_fuse_vae_decoder_feat: the no-tape forward on an exact-2x geometry upsamples, concatenates and classifies in one
+    # kernel (ops.upsample_cat_classify); False = always the composed path (resize + two-source conv)
+    fused_classifier = True
+
     def __init__(self, in_channels, in_keys, channels, *, num_classes, dropout_ratio=0.1, conv_cfg=None, norm_cfg=None,
                  act_cfg=None, in_index=-1, input_transform='multiple_select', decoder_params=None, ignore_index=255,
                  align_corners=False, init_cfg=None, concat_attention_to_conv_seg=False,
                  final_fuse_vae_decoder_feat=False):
         super().__init__()
-        if concat_attention_to_conv_seg or final_fuse_vae_decoder_feat:
-            raise NotImplementedError("concat_attention_to_conv_seg / final_fuse_vae_decoder_feat (no shipped config) are "
-                                      "not built")
+        if concat_attention_to_conv_seg:
+            raise NotImplementedError("concat_attention_to_conv_seg (no shipped config) is not built")
         assert input_transform == 'multiple_select' and not align_corners
         self.in_channels, self.in_index, self.in_keys = list(in_channels), list(in_index), list(in_keys)
         self.channels, self.num_classes, self.dropout_ratio = channels, num_classes, dropout_ratio
         self.ignore_index, self.align_corners = ignore_index, align_corners
-        self.final_fuse_vae_decoder_feat = False
+        self.final_fuse_vae_decoder_feat = bool(final_fuse_vae_decoder_feat)
+        self.last_route = None    # flagged head: "fused" / "composed", what the last forward_tokens took
         embed_dims = decoder_params['embed_dims']
         if isinstance(embed_dims, int):
             embed_dims = [embed_dims] * len(self.in_index)
@@ -251,7 +322,12 @@ class DAFormerHead(nn.Module):
         self.embed_layers = nn.ModuleDict({str(i): MLP(c, e) for i, c, e in zip(self.in_index, self.in_channels, embed_dims)})
         fusion_cfg.pop('align_corners', None)
         self.fuse_layer = ASPPWrapper(in_channels=sum(embed_dims), channels=channels, **fusion_cfg)
-        self.conv_seg = nn.Conv2d(channels, num_classes, kernel_size=1)   # parameter container (mmseg's name)
+        cls_in = channels
+        if self.final_fuse_vae_decoder_feat:   # the full-resolution s0 joins at the classifier (daformer_head.py:575-589)
+            self.vae_decoder_feat_proj = nn.Sequential(
+                NarrowBottleneckBlock(128, self.FUSE_PROJ_CHANNELS, bottleneck_channels=32))
+            cls_in = channels + self.FUSE_PROJ_CHANNELS
+        self.conv_seg = nn.Conv2d(cls_in, num_classes, kernel_size=1)     # parameter container (mmseg's name)
         self.dropout = nn.Identity()                                      # Dropout2d(dropout_ratio): see _dropout_scale
         self.dropout_generator = None       # torch.Generator for the Dropout2d masks (None: the device's default RNG)
         self.dropout_scale_override = None  # tests: a fixed f32 [B, channels] scale (keep / (1 - p)) instead of a draw
@@ -300,6 +376,12 @@ class DAFormerHead(nn.Module):
         """list of feature Toks (in ``in_keys`` order) -> f32 logit tokens Tok [B*H0*W0, Kp] (first num_classes columns
         valid).  Train mode: batch-statistic BatchNorm + Dropout2d; ``tape`` (a dict) receives what
         :meth:`backward_tokens` needs."""
+        s0 = None
+        if self.final_fuse_vae_decoder_feat:
+            # the scales are fused at half of s0's size (daformer_head.py:721-723); s0 itself joins at the classifier
+            s0 = x[0]
+            x = list(x)
+            x[0] = Tok(ops.resize_bilinear(s0.t, s0.B, s0.H, s0.W, s0.H // 2, s0.W // 2), s0.B, s0.H // 2, s0.W // 2)
         x0 = x[0]
         M0 = x0.t.shape[0]
         cat = torch.empty((M0, sum(self.embed_dims)), dtype=x0.t.dtype, device=x0.t.device)
@@ -324,11 +406,33 @@ class DAFormerHead(nn.Module):
             scale = self._dropout_scale(h.B, h.t.device)
             hd = ops.scale_channels(h.t, scale, h.B, h.HW)
         w, b = self._cls_weights(h.t.dtype, Kp)
+        if s0 is not None:
+            return self._fuse_classify(s0, h, hd, w, b, Kp, x, scale, fuse_tape, tape)
         logits = ops.conv2d(hd, w, h.B, h.H, h.W, N=Kp, bias=b, out_f32=True)
         if tape is not None:
             assert self.training, "the head's backward is the train-mode one"
             tape.update(x=list(x), fuse=fuse_tape, hd=hd, scale=scale, geom=(h.B, h.H, h.W))
         return Tok(logits, h.B, h.H, h.W)
+
+    def _fuse_classify(self, s0, h, hd, w, b, Kp, x, scale, fuse_tape, tape):
+        """cls_seg of the flagged head (daformer_head.py:689-698): the (dropped-out) fused map ``hd`` resized to s0's size,
+        concatenated with vae_decoder_feat_proj(s0), then the 1x1 classifier over both.  Without a tape and on an exact 2x
+        geometry the upsampled map is never written (ops.upsample_cat_classify); otherwise -- odd sizes, and the training
+        forward whose backward needs the upsampled operand -- resize + the two-source conv."""
+        proj_tape = [] if tape is not None else None
+        proj = self.vae_decoder_feat_proj[0](s0, tape=proj_tape)
+        if tape is None and self.fused_classifier and (s0.H, s0.W) == (2 * h.H, 2 * h.W):
+            self.last_route = "fused"
+            logits = ops.upsample_cat_classify(hd, proj.t, w, b, h.B, h.H, h.W)
+        else:
+            self.last_route = "composed"
+            up = ops.resize_bilinear(hd, h.B, h.H, h.W, s0.H, s0.W)
+            logits = ops.conv2d(up, w, s0.B, s0.H, s0.W, N=Kp, x2=proj.t, bias=b, out_f32=True)
+        if tape is not None:
+            assert self.training, "the head's backward is the train-mode one"
+            tape.update(x=list(x), fuse=fuse_tape, hd=hd, scale=scale, geom=(h.B, h.H, h.W), s0=s0, up=up, proj=proj,
+                        proj_rec=proj_tape[0])
+        return Tok(logits, s0.B, s0.H, s0.W)
 
     def backward_tokens(self, tape, dlogits):
         """dlogits: [M0, ld >= num_classes] tokens of the compute dtype (columns beyond num_classes zero).  Returns
@@ -342,11 +446,26 @@ class DAFormerHead(nn.Module):
         # ---- conv_seg ----
         N = dlogits.shape[1]
         db = ops.zeros_f32((N,), dlogits.device)
-        dwp = ops.conv2d_wgrad(hd, dlogits, B, H, W, dbias=db)                        # [N, C]; bias sums by the same launch
-        grads["conv_seg.weight"] = dwp[:K, :C].reshape(K, C, 1, 1).contiguous()
-        grads["conv_seg.bias"] = db[:K].contiguous()
-        wt = self._cls_dgrad_weights(dtype, N)
-        dhd = ops.conv2d_dgrad(dlogits, wt, B, H, W, C=wt.shape[0])
+        ds0 = None
+        if self.final_fuse_vae_decoder_feat:
+            # the classifier read [up | proj] at s0's size: its data gradient splits into the adjoint of the up-resize
+            # (towards the fusion stage) and the projection block's output gradient (towards s0)
+            s0, Cp = tape["s0"], self.FUSE_PROJ_CHANNELS
+            dwp = ops.conv2d_wgrad(tape["up"], dlogits, B, s0.H, s0.W, x2=tape["proj"].t, dbias=db)     # [N, C + Cp]
+            grads["conv_seg.weight"] = dwp[:K, :C + Cp].reshape(K, C + Cp, 1, 1).contiguous()
+            grads["conv_seg.bias"] = db[:K].contiguous()
+            wt = self._cls_dgrad_weights(dtype, N)
+            dcls = ops.conv2d_dgrad(dlogits, wt, B, s0.H, s0.W, C=wt.shape[0])                            # [M0, C + Cp]
+            dhd = ops.resize_bilinear_backward(dcls[:, :C], B, H, W, s0.H, s0.W)
+            ds0, g = self.vae_decoder_feat_proj[0].backward(tape["proj_rec"], dcls[:, C:C + Cp])
+            for k_, v in g.items():
+                grads["vae_decoder_feat_proj.0." + k_] = v
+        else:
+            dwp = ops.conv2d_wgrad(hd, dlogits, B, H, W, dbias=db)                    # [N, C]; bias sums by the same launch
+            grads["conv_seg.weight"] = dwp[:K, :C].reshape(K, C, 1, 1).contiguous()
+            grads["conv_seg.bias"] = db[:K].contiguous()
+            wt = self._cls_dgrad_weights(dtype, N)
+            dhd = ops.conv2d_dgrad(dlogits, wt, B, H, W, C=wt.shape[0])
         dh = dhd if scale is None else ops.scale_channels(dhd, scale, B, H * W)
         # ---- fusion (sep-ASPP + bottleneck) ----
         dcat = self.fuse_layer.backward(tape["fuse"], dh, grads, "fuse_layer.")
@@ -364,7 +483,14 @@ class DAFormerHead(nn.Module):
                 grads[f"embed_layers.{i}.proj.{k_}"] = v
             dfeats.append(df)
             off += e
+        if ds0 is not None:   # s0's two paths: the adjoint of the down-resize behind its MLP, and the projection block's dx
+            s0 = tape["s0"]
+            dfeats[0] = ops.add(ops.resize_bilinear_backward(dfeats[0], s0.B, s0.H, s0.W, x0.H, x0.W), ds0)
         return dfeats, grads
+
+    def _cls_splits(self):
+        """channel counts of the classifier's concatenated sources (None: the one fused map)"""
+        return [self.channels, self.FUSE_PROJ_CHANNELS] if self.final_fuse_vae_decoder_feat else None
 
     def _cls_dgrad_weights(self, dtype, N):
         key = (dtype, N, self.conv_seg.weight._version, self.conv_seg.weight.data_ptr())
@@ -373,7 +499,7 @@ class DAFormerHead(nn.Module):
             with torch.no_grad():
                 w = self.conv_seg.weight.detach().float()
                 w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, N - w.shape[0]))
-                wp = packing.pack_conv_weight(w, dtype, ops.k_tile(dtype))              # [N, C]
+                wp = packing.pack_conv_weight(w, dtype, ops.k_tile(dtype), self._cls_splits())   # [N, C]
                 c = (key, ops.pack_dgrad_weights(wp, 1))
             ops.note_build()
             self.__dict__["_cls_dgrad_cache"] = c
@@ -388,7 +514,7 @@ class DAFormerHead(nn.Module):
                 b = self.conv_seg.bias.detach().float()
                 w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, Kp - w.shape[0]))
                 b = torch.nn.functional.pad(b, (0, Kp - b.shape[0])).contiguous()
-                c = (key, packing.pack_conv_weight(w, dtype, ops.k_tile(dtype)), b)
+                c = (key, packing.pack_conv_weight(w, dtype, ops.k_tile(dtype), self._cls_splits()), b)
             ops.note_build()
             self.__dict__["_cls_cache"] = c
         return c[1], c[2]

@@ -130,7 +130,8 @@ class Conv2d(_Packed):
         if norm is not None:
             # folding the norm into the conv re-applies it once per output-channel tile: measured on MI355X it pays up to
             # 256 output channels (ops.FUSE_GN_MAX_N); wider layers run gn_apply once + the plain conv
-            if self.out_channels <= ops.FUSE_GN_MAX_N and ops.can_fuse_groupnorm(
+            # (and up to 32 groups: the halo kernels keep one {mean, rstd} pair per group in a 32-entry LDS table)
+            if self.out_channels <= ops.FUSE_GN_MAX_N and norm.num_groups <= ops.FUSE_GN_MAX_GROUPS and ops.can_fuse_groupnorm(
                     x.H, x.W, self.kernel_size, self.stride, self.padding, self.asym_pad, upsample):
                 srcs = [x] if x2 is None else [x, x2]
                 sts = []

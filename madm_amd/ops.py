@@ -140,6 +140,7 @@ FORCE_SPLITK = None
 # tests/test_parity_gpu.py::test_bench_workloads_have_tuned_rows
 TILE_LOG = None
 FUSE_GN = True   # fold GroupNorm(+SiLU) into eligible 3x3 convs (debug switch)
+FUSE_GN_MAX_GROUPS = 32   # ... whose norm has at most 32 groups (madm_conv2d_fwd refuses more: a 32-entry LDS table)
 FUSE_GN_MAX_N = 256   # ... whose output has at most 256 channels: the
 # transform is redone once per output-channel tile, so on the wide UNet layers (320 .. 1280 channels, 5 .. 20 tiles of 64) a
 # stand-alone GroupNorm pass + the plain conv is less total work.  Same-box A/B with both variants tuned (images/s,
@@ -1024,6 +1025,36 @@ def resize_bilinear(x, B, IH, IW, OH, OW, out=None):
     assert out.shape == (B * OH * OW, C) and out.stride(1) == 1 and out.dtype == x.dtype
     check(lib.madm_resize_bilinear(dtype_code(x), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), B, IH, IW, OH, OW,
                                    C, _stream()), "madm_resize_bilinear")
+    return out
+
+
+_headfuse = None
+
+
+def upsample_cat_classify(hd, proj, w, bias, B, h, w_lo, out=None):
+    """f32 out [B*2h*2w, Kp] = conv1x1([bilinear 2x of hd [B*h*w, C1] | proj [B*2h*2w, C2]], w [Kp, C1+C2]) + bias in one
+    pass: the last step of DAFormerHead(final_fuse_vae_decoder_feat=True) without the upsampled map (libmadm_headfuse.so,
+    include/madm_headfuse.h; loaded by the first call).  hd / proj / w / out may be column windows of wider buffers."""
+    global _headfuse
+    if _headfuse is None:
+        from . import _lib_headfuse
+        _headfuse = _lib_headfuse
+    _need_cuda(hd, proj, w, bias, out)
+    H, W = 2 * h, 2 * w_lo
+    C1, C2, Kp = hd.shape[1], proj.shape[1], w.shape[0]
+    assert hd.stride(1) == 1 and hd.shape[0] == B * h * w_lo, (hd.shape, B, h, w_lo)
+    assert proj.stride(1) == 1 and proj.shape[0] == B * H * W and proj.dtype == hd.dtype, (proj.shape, B, H, W)
+    assert w.dtype == hd.dtype and w.stride(1) == 1 and w.shape[1] == C1 + C2, (w.shape, C1, C2)
+    assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == Kp
+    if out is None:
+        out = torch.empty((B * H * W, Kp), dtype=torch.float32, device=hd.device)
+    assert out.shape == (B * H * W, Kp) and out.stride(1) == 1 and out.dtype == torch.float32
+    es = hd.element_size()
+    with _Prof("upsample_cat_classify" + _SUFFIX[hd.dtype], 2.0 * B * H * W * Kp * (C1 + C2), f"M{B * H * W} N{Kp} K{C1 + C2}",
+               (hd.numel() + proj.numel() + w.numel()) * es + out.numel() * 4):
+        _headfuse.check(_headfuse.lib.mhf_upsample_cat_classify(
+            dtype_code(hd), hd.data_ptr(), hd.stride(0), proj.data_ptr(), proj.stride(0), w.data_ptr(), w.stride(0),
+            bias.data_ptr(), out.data_ptr(), out.stride(0), B, h, w_lo, H, W, C1, C2, Kp, _stream()), "mhf_upsample_cat_classify")
     return out
 
 
