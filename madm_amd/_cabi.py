@@ -1,7 +1,8 @@
-"""Reader of the C ABI headers (include/madm_hip.h, include/madm_data.h, include/madm_det.h): the ctypes structures, signatures
-and constants that ``_lib.py`` / ``_lib_data.py`` / ``_lib_det.py`` bind come from the text every ``.hip`` file is compiled against, not from a
-table kept next to it.  Standard library only: no torch, no library is loaded (tools/conv_plan_fixture.py and the host
-tests use it on their own).
+"""Reader of the C ABI headers (include/madm_hip.h, madm_data.h, madm_det.h, madm_headfuse.h): the ctypes structures,
+signatures and constants that ``_lib.py`` / ``_lib_data.py`` / ``_lib_det.py`` / ``_lib_headfuse.py`` bind come from the text
+every ``.hip`` file is compiled against, not from a table kept next to it.  Standard library only: no torch; ``parse``
+loads no library (tools/conv_plan_fixture.py and the host tests use it on their own), ``load`` at the end is the one
+loader the binding modules share.
 
 It reads the C these headers are written in and refuses the rest with the header's line (``HeaderError``), never
 guessing a type: ``#define NAME <integer>``; ``typedef enum { NAME = <integer>, ... } name;``; ``typedef struct { ... }
@@ -14,6 +15,7 @@ parameters, unknown type names and pointers to structs not seen yet are errors.
 import ctypes
 import os
 import re
+import types
 
 _SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned long long": ctypes.c_ulonglong,
             "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
@@ -140,3 +142,36 @@ def parse_packaged(name):
     if not os.path.exists(path):
         raise ImportError(f"{path} not found: the ctypes binding of the library is read from this header")
     return parse(path)
+
+
+def load(header, libname, override, version_fn, version, last_error_fn, error, no_fallback, version_from="this binding is for"):
+    """The one loader behind ``_lib.py``, ``_lib_data.py``, ``_lib_det.py`` and ``_lib_headfuse.py``: binds madm_amd/<libname>,
+    or the file ``override`` names (what the module's MADM_*_LIB environment variable holds), from include/<header>.  Returns a
+    namespace of ABI (the parsed header), SYMBOLS (``ABI.symbols()``), LIB_PATH, lib (every declared symbol typed),
+    last_error() and check(rc, what), which raises ``error`` with the library's text on a non-zero status.  ``version`` is
+    what ``version_fn`` must return: an integer, or the name of the header's constant that holds it.  ImportError when the
+    file is missing (names the path and the make line, ends with ``no_fallback``) or of another ABI version ("rebuild");
+    AttributeError when a declared symbol is not exported."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    abi = parse_packaged(header)
+    path = override or os.path.join(here, libname)
+    if not os.path.exists(path):
+        raise ImportError(f"{path} not found: build it with `make -C {os.path.join(here, 'csrc')}` "
+                          f"(or __graft_entry__.build()); {no_fallback}")
+    lib = ctypes.CDLL(path)
+    for name, restype, argtypes in abi.symbols():
+        fn = getattr(lib, name)  # AttributeError if the export is missing
+        fn.restype = restype
+        fn.argtypes = argtypes
+    want, got = (version if isinstance(version, int) else abi.constants[version]), getattr(lib, version_fn)()
+    if got != want:
+        raise ImportError(f"{path} has ABI version {got}, {version_from} {want}: rebuild")
+
+    def last_error():
+        return getattr(lib, last_error_fn)().decode("utf-8", "replace")
+
+    def check(rc, what):
+        if rc != 0:
+            raise error(f"{what} failed (status {rc}): {last_error()}")
+
+    return types.SimpleNamespace(ABI=abi, SYMBOLS=abi.symbols(), LIB_PATH=path, lib=lib, last_error=last_error, check=check)

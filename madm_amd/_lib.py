@@ -5,15 +5,19 @@ constants are read from the header by ``_cabi.py``; the names below only bind th
 if the shared object or the header is missing, a declared symbol is not exported, or the library was built for another
 ABI version, importing this module raises.
 """
-import ctypes
 import os
 
 from . import _cabi
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("MADM_HIP_LIB") or os.path.join(_HERE, "libmadm_hip.so")   # env override: A/B kernel builds
 
-ABI = _cabi.parse_packaged("madm_hip.h")
+class MadmHipError(RuntimeError):
+    pass
+
+
+_B = _cabi.load(header="madm_hip.h", libname="libmadm_hip.so", override=os.environ.get("MADM_HIP_LIB"),   # A/B kernel builds
+                version_fn="madm_abi_version", version="MADM_ABI_VERSION", version_from="include/madm_hip.h declares",
+                last_error_fn="madm_last_error", error=MadmHipError, no_fallback="madm_amd has no CPU fallback")
+ABI, SYMBOLS, LIB_PATH, lib, last_error, check = _B.ABI, _B.SYMBOLS, _B.LIB_PATH, _B.lib, _B.last_error, _B.check
 _C = ABI.constants
 
 MADM_F32, MADM_BF16, MADM_F16 = _C["MADM_F32"], _C["MADM_BF16"], _C["MADM_F16"]
@@ -29,31 +33,6 @@ Conv2dWgradArgs = ABI.struct("madm_conv2d_wgrad_args")
 AttentionArgs = ABI.struct("madm_attention_args")
 AttentionBwdArgs = ABI.struct("madm_attention_bwd_args")
 VisTile = ABI.struct("madm_vis_tile")
-
-SYMBOLS = ABI.symbols()   # every symbol include/madm_hip.h declares: (name, restype, argtypes)
-
-
-class MadmHipError(RuntimeError):
-    pass
-
-
-def _load():
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} not found: build it with `make -C {os.path.join(_HERE, 'csrc')}` "
-            "(or __graft_entry__.build()); madm_amd has no CPU fallback")
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, restype, argtypes in SYMBOLS:
-        fn = getattr(lib, name)  # AttributeError if the export is missing
-        fn.restype = restype
-        fn.argtypes = argtypes
-    if lib.madm_abi_version() != _C["MADM_ABI_VERSION"]:
-        raise ImportError(f"{LIB_PATH} has ABI version {lib.madm_abi_version()}, include/madm_hip.h declares "
-                          f"{_C['MADM_ABI_VERSION']}: rebuild")
-    return lib
-
-
-lib = _load()
 
 
 class _PoisonedLib:
@@ -85,8 +64,3 @@ class _PoisonedLib:
 if int(os.environ.get("MADM_DEBUG_POISON_LDS", "0")):
     lib = _PoisonedLib(lib)
 
-
-def check(rc, what):
-    if rc != 0:
-        msg = lib.madm_last_error().decode("utf-8", "replace")
-        raise MadmHipError(f"{what} failed (status {rc}): {msg}")

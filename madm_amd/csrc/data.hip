@@ -11,41 +11,13 @@
 //
 // Memory safety does not depend on the tables' contents: every window is clamped to the source, every tap count to the
 // table width and to the footprint held in LDS.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
+#include "entry.hpp"
 #include "madm_data.h"
 #include "png_unfilter.hpp"
 
 namespace {
 
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-        return MDATA_ERR_LAUNCH;
-    }
-    return MDATA_OK;
-}
-
-#define MDATA_REQUIRE(cond, ...)           \
-    do {                                   \
-        if (!(cond)) {                     \
-            set_error(__VA_ARGS__);        \
-            return MDATA_ERR_INVALID_ARG;  \
-        }                                  \
-    } while (0)
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+#define MDATA_REQUIRE(...) ENTRY_REQUIRE(MDATA_ERR_INVALID_ARG, __VA_ARGS__)
 
 constexpr int TY = 16, TX = 64;                           // crop pixels per workgroup (256 threads, 4 rows each)
 constexpr int FOOT = TY * 8 + MDATA_MAX_TAPS + 1;         // source rows a tile's vertical pass can touch at scale <= 8
@@ -256,7 +228,7 @@ extern "C" int mdata_prep_image_u8(const uint8_t* src, int C, int src_ld, int in
     MDATA_REQUIRE(gy <= 65535u, "prep_image_u8: crop of %d rows is too tall", ch);
     ImageGeom g{C, src_ld, in_h, in_w, hk, vk, y0, x0, ch, cw, flip, out_ld, out_plane};
     prep_image_kernel<<<dim3(gx, gy), 256, 0, (hipStream_t)stream>>>(g, src, hbounds, hcoef, vbounds, vcoef, out);
-    return check_launch("prep_image_kernel");
+    return check_launch("prep_image_kernel", MDATA_ERR_LAUNCH);
 }
 
 extern "C" int mdata_prep_label_u8(const uint8_t* src, int src_px, int src_ld, int in_h, int in_w, const int32_t* ytab,
@@ -281,7 +253,7 @@ extern "C" int mdata_prep_label_u8(const uint8_t* src, int src_px, int src_ld, i
     MDATA_REQUIRE(gy <= 65535u, "prep_label_u8: crop of %d rows is too tall", ch);
     LabelGeom g{src_px, src_ld, in_h, in_w, y0, x0, ch, cw, flip, out_ld};
     prep_label_kernel<<<dim3(gx, gy), 256, 0, (hipStream_t)stream>>>(g, src, ytab, xtab, lut1, lut2, hist, out);
-    return check_launch("prep_label_kernel");
+    return check_launch("prep_label_kernel", MDATA_ERR_LAUNCH);
 }
 
 extern "C" int mdata_png_unfilter(const uint8_t* in, size_t in_len, uint8_t* out, size_t out_len, int height,

@@ -8,38 +8,14 @@
 // partial to workspace[b][slice][accumulator][column].  Stage 2 (fold_kernel): one thread per (b, accumulator, column)
 // adds the slices in index order in f64 and updates the output once.  No atomics anywhere; slices, lanes and trips depend
 // on the shapes and the dtype only.  HBM-bound streaming kernels: nothing here is tuned beyond the load batching.
-#include <stdarg.h>
-#include <stdio.h>
 #include "common.hpp"   // dtype traits and chunk conversion (device helpers only: nothing here links to libmadm_hip.so)
+#include "entry.hpp"
 #include "madm_det.h"
+#include "shared_math.hpp"   // act_grad_f, gn_bwd_fold_stats
 
 namespace {
 
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-        return MDET_ERR_LAUNCH;
-    }
-    return MDET_OK;
-}
-
-#define MDET_REQUIRE(cond, ...)           \
-    do {                                  \
-        if (!(cond)) {                    \
-            set_error(__VA_ARGS__);       \
-            return MDET_ERR_INVALID_ARG;  \
-        }                                 \
-    } while (0)
+#define MDET_REQUIRE(...) ENTRY_REQUIRE(MDET_ERR_INVALID_ARG, __VA_ARGS__)
 
 #define MDET_DISPATCH_DTYPE(dtype, ...)   \
     do {                                  \
@@ -55,7 +31,6 @@ int check_launch(const char* what) {
         }                                 \
     } while (0)
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 inline bool dtype_ok(int dtype) { return dtype == MDET_F32 || dtype == MDET_BF16 || dtype == MDET_F16; }
 inline int epc_of(int dtype) { return dtype == MDET_F32 ? 4 : 8; }
 
@@ -229,50 +204,7 @@ struct GnStatsF {
 };
 
 // ---- GroupNorm backward sums ------------------------------------------------------------------------------------------------
-// act_grad_f and gn_fold_stats are norm_bwd.hip's (act_grad_f, gn_bwd_fold_stats), statement for statement: xh and dz
-// here are the values madm_groupnorm_bwd_apply forms from the same statistics.
-__device__ __forceinline__ float act_grad_f(float z, float dy, int act) {
-    if (act == 1) {
-        const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
-        return dy * sg * (1.0f + z * (1.0f - sg));
-    }
-    if (act == 2) return z > 0.f ? dy : 0.f;
-    return dy;
-}
-
-__device__ __forceinline__ void gn_fold_stats(float* r, float* mr, int b, int HW, int C, int c_off, int Ctot, int G,
-                                              const double* __restrict__ sums1, int C1,
-                                              const double* __restrict__ sums2, float eps) {
-    const int cpg = Ctot / G, C2 = Ctot - C1;
-    const double inv_cnt = 1.0 / ((double)HW * (double)cpg);
-    for (int g0 = 0; g0 < G; g0 += 32) {
-        const int g = g0 + ((int)threadIdx.x >> 3), l = threadIdx.x & 7;
-        double s = 0.0, q = 0.0;
-        if (g < G) {
-            for (int ch = g * cpg + l; ch < (g + 1) * cpg; ch += 8) {
-                const double* src = (ch < C1) ? sums1 + ((size_t)b * C1 + ch) * 2 : sums2 + ((size_t)b * C2 + (ch - C1)) * 2;
-                s += src[0];
-                q += src[1];
-            }
-        }
-#pragma unroll
-        for (int o = 1; o < 8; o <<= 1) {
-            s += __shfl_xor(s, o);
-            q += __shfl_xor(q, o);
-        }
-        if (g < G) {
-            const double mean = s * inv_cnt;
-            double var = q * inv_cnt - mean * mean;
-            if (var < 0.0) var = 0.0;
-            const float rstd = __builtin_amdgcn_rsqf((float)var + eps);
-            for (int ch = g * cpg + l; ch < (g + 1) * cpg; ch += 8) {
-                const int c = ch - c_off;
-                if (c >= 0 && c < C) { r[c] = rstd; mr[c] = -(float)mean * rstd; }
-            }
-        }
-    }
-}
-
+// xh and dz are the values madm_groupnorm_bwd_apply forms from the same statistics: shared_math.hpp defines both once
 struct GnCol {
     float cr[8], cm[8], cg[8], cb[8];
 };
@@ -293,7 +225,7 @@ struct GnBwdSumsF {
             cst[2 * C + c] = gamma[c_off + c];
             cst[3 * C + c] = beta[c_off + c];
         }
-        gn_fold_stats(cst, cst + C, b, HW, C, c_off, Ctot, G, sums1, C1, sums2, eps);
+        gn_bwd_fold_stats(cst, cst + C, b, HW, C, c_off, Ctot, G, sums1, C1, sums2, eps);
     }
     template <typename T> __device__ void column(Col& k, const float* cst, int q) const {
 #pragma unroll
@@ -338,6 +270,7 @@ __global__ __launch_bounds__(256) void gn_bwd_params_kernel(const double* __rest
 // ---- LayerNorm parameter gradients ----------------------------------------------------------------------------------------------
 // Row statistics first, one wave per row with layernorm_bwd_kernel's arithmetic (norm_bwd.hip: lane sums over its chunks,
 // xor shuffles, 1 / sqrtf) into st[row] = (mean, rstd); the skeleton then reads them per row.
+// A local copy, not in shared_math.hpp: calling even the 1 / sqrtf through a shared helper reschedules this kernel.
 template <typename T>
 __global__ __launch_bounds__(256) void ln_rowstats_kernel(const T* __restrict__ x, int M, int C, float eps,
                                                           float2* __restrict__ st) {
@@ -467,11 +400,11 @@ int run(const char* what, int dtype, const F& f, int B, int R, int C, int slices
     MDET_REQUIRE(lds <= 64 * 1024, "%s: C = %d too large", what, C);
     const dim3 grid((unsigned)g.slices, (unsigned)B);
     MDET_DISPATCH_DTYPE(dtype, (partials_kernel<T, F><<<grid, 256, lds, s>>>(f, g, ws)));
-    int rc = check_launch(what);
+    int rc = check_launch(what, MDET_ERR_LAUNCH);
     if (rc != MDET_OK) return rc;
     const size_t n = (size_t)B * F::NACC * C;
     fold_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(ws, B, g.slices, F::NACC, C, out);
-    return check_launch(what);
+    return check_launch(what, MDET_ERR_LAUNCH);
 }
 
 }  // namespace
@@ -554,7 +487,7 @@ int mdet_groupnorm_bwd_params(const double* bsums, int B, int Ctot, float* dgamm
     MDET_REQUIRE(aligned(bsums, 8) && aligned(dgamma, 4) && aligned(dbeta, 4),
                  "groupnorm_bwd_params: bsums must be 8-byte aligned, dgamma / dbeta 4-byte aligned");
     gn_bwd_params_kernel<<<dim3((unsigned)((Ctot + 255) / 256)), 256, 0, (hipStream_t)stream>>>(bsums, B, Ctot, dgamma, dbeta);
-    return check_launch("groupnorm_bwd_params");
+    return check_launch("groupnorm_bwd_params", MDET_ERR_LAUNCH);
 }
 
 int mdet_layernorm_bwd_params(int dtype, const void* x, const void* dy, int M, int C, float eps, float* dgamma,
@@ -569,7 +502,7 @@ int mdet_layernorm_bwd_params(int dtype, const void* x, const void* dy, int M, i
     float2* st = reinterpret_cast<float2*>((float*)workspace + ws_floats(1, slices, 2, C));   // C % 4 == 0: 16-byte aligned
     hipStream_t s = (hipStream_t)stream;
     MDET_DISPATCH_DTYPE(dtype, (ln_rowstats_kernel<T><<<dim3((unsigned)((M + 3) / 4)), 256, 0, s>>>((const T*)x, M, C, eps, st)));
-    const int rc2 = check_launch("layernorm_bwd_params");
+    const int rc2 = check_launch("layernorm_bwd_params", MDET_ERR_LAUNCH);
     if (rc2 != MDET_OK) return rc2;
     const LnParamsF f{x, dy, st, C};
     const FoldOut o{nullptr, 0, 0, dgamma, dbeta, 0, 0};

@@ -9,31 +9,14 @@
 // fragment is the packed classifier row (class = lane & 15 of the 16-class tile), read from global memory (a few KiB, shared
 // by every workgroup: cache resident).  The C2 steps read the full-resolution operand straight from global memory.
 // mma16 (common.hpp) leaves pixel = lane & 15, classes 4 (lane >> 4) .. + 3 in a lane: one 16-byte store per class tile.
-#include <stdarg.h>
-#include <stdio.h>
 #include "common.hpp"   // dtype traits, chunk conversion, mma16 (device helpers only: nothing here links to libmadm_hip.so)
+#include "entry.hpp"
 #include "madm_headfuse.h"
+#include "shared_math.hpp"   // bilinear_coord
 
 namespace {
 
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-#define MHF_REQUIRE(cond, ...)           \
-    do {                                 \
-        if (!(cond)) {                   \
-            set_error(__VA_ARGS__);      \
-            return MHF_ERR_INVALID_ARG;  \
-        }                                \
-    } while (0)
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+#define MHF_REQUIRE(...) ENTRY_REQUIRE(MHF_ERR_INVALID_ARG, __VA_ARGS__)
 
 constexpr int TH = MHF_TILE_H, TW = MHF_TILE_W, HALO_H = TH + 2, HALO_W = TW + 2;
 
@@ -46,16 +29,6 @@ struct Params {
     int ldh, ldp, ldw, ldo;
     int B, h, w_lo, H, W, C1, C2, Kp;
 };
-
-// PyTorch F.interpolate(mode='bilinear', align_corners=False) source index / weight at scale 1/2 (spatial.hip's bilinear_coord)
-__device__ __forceinline__ void coord2x(int o, int in_size, int& i0, int& i1, float& l1) {
-    float src = ((float)o + 0.5f) * 0.5f - 0.5f;
-    if (src < 0.f) src = 0.f;
-    i0 = (int)src;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-}
 
 template <typename T, int NT>
 __global__ __launch_bounds__(256) void upsample_cat_classify_kernel(const Params p) {
@@ -79,7 +52,7 @@ __global__ __launch_bounds__(256) void upsample_cat_classify_kernel(const Params
     const int ox = 2 * lx0 + j, oxc = min(ox, p.W - 1);
     int x0, x1;
     float fx;
-    coord2x(oxc, p.w_lo, x0, x1, fx);
+    bilinear_coord(oxc, p.w_lo, 0.5f, x0, x1, fx);   // the source is half the output
     x0 -= lx0 - 1;
     x1 -= lx0 - 1;
 
@@ -92,7 +65,7 @@ __global__ __launch_bounds__(256) void upsample_cat_classify_kernel(const Params
         const int oy = 2 * ly0 + 2 * wave + t, oyc = min(oy, p.H - 1);
         int y0, y1;
         float fy;
-        coord2x(oyc, p.h, y0, y1, fy);
+        bilinear_coord(oyc, p.h, 0.5f, y0, y1, fy);
         y0 -= ly0 - 1;
         y1 -= ly0 - 1;
         o00[t] = (y0 * HALO_W + x0) * S + g;
@@ -172,12 +145,7 @@ int launch(const Params& p, hipStream_t s) {
         upsample_cat_classify_kernel<T, 2><<<grid, 256, lds, s>>>(p);
     else
         upsample_cat_classify_kernel<T, 4><<<grid, 256, lds, s>>>(p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("upsample_cat_classify: launch failed: %s", hipGetErrorString(e));
-        return MHF_ERR_LAUNCH;
-    }
-    return MHF_OK;
+    return check_launch("upsample_cat_classify", MHF_ERR_LAUNCH);
 }
 
 }  // namespace
@@ -192,7 +160,7 @@ int mhf_upsample_cat_classify(int dtype, const void* hd, int ldh, const void* pr
                               int C1, int C2, int Kp, void* stream) {
     MHF_REQUIRE(dtype == MHF_F32 || dtype == MHF_BF16 || dtype == MHF_F16, "upsample_cat_classify: unknown dtype %d", dtype);
     MHF_REQUIRE(hd && proj && w && bias && out, "upsample_cat_classify: null tensor pointer");
-    MHF_REQUIRE(aligned16(hd) && aligned16(proj) && aligned16(w) && aligned16(bias) && aligned16(out),
+    MHF_REQUIRE(aligned(hd, 16) && aligned(proj, 16) && aligned(w, 16) && aligned(bias, 16) && aligned(out, 16),
                 "upsample_cat_classify: hd / proj / w / bias / out must be 16-byte aligned");
     MHF_REQUIRE(B > 0 && h > 0 && w_lo > 0, "upsample_cat_classify: bad sizes B=%d h=%d w=%d", B, h, w_lo);
     MHF_REQUIRE(H == 2 * h && W == 2 * w_lo, "upsample_cat_classify: the output %d x %d is not twice the source %d x %d", H, W, h, w_lo);

@@ -2,18 +2,9 @@
 // bilinear resize (tokens and NCHW images), depthwise dilated 3x3 conv (+ folded BatchNorm + ReLU),
 // tanh-gated prompt / time conditioning, per-pixel argmax.  All HBM-bound streaming kernels.
 #include "common.hpp"
+#include "shared_math.hpp"   // bilinear_coord
 
 namespace {
-
-// PyTorch F.interpolate(mode='bilinear', align_corners=False) source index / weight
-__device__ __forceinline__ void bilinear_coord(int o, int in_size, float scale, int& i0, int& i1, float& l1) {
-    float src = ((float)o + 0.5f) * scale - 0.5f;
-    if (src < 0.f) src = 0.f;
-    i0 = (int)src;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-}
 
 // channels-last: in [B*IH*IW][ldi] (C channels) -> out [B*OH*OW][ldo] (out already points at its column offset)
 template <typename T>

@@ -4,17 +4,9 @@
 // masked L1 / L2 on the latents) and the backward of the tanh-gated prompt / time conditioning.  In the reference all of
 // these are torch autograd nodes behind ``losses.backward()`` (engine/train_loop.py:203-217).  HBM-bound streaming kernels.
 #include "common.hpp"
+#include "shared_math.hpp"   // bilinear_coord
 
 namespace {
-
-__device__ __forceinline__ void bilinear_coord(int o, int in_size, float scale, int& i0, int& i1, float& l1) {
-    float src = ((float)o + 0.5f) * scale - 0.5f;   // F.interpolate(bilinear, align_corners=False), as spatial.hip
-    if (src < 0.f) src = 0.f;
-    i0 = (int)src;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-}
 
 // y[b][p][c] = x[b][p][c] * s[b][c]: Dropout2d (s = keep-mask / (1 - p) per (image, channel)); its own backward on dy
 template <typename T>

@@ -5,6 +5,7 @@
 // coalesced along x, a low-resolution logits tile is sampled bilinearly per pixel and class (never materialised).  No LDS,
 // no scratch: the table travels as kernel arguments and is read from there.
 #include "common.hpp"
+#include "shared_math.hpp"   // bilinear_coord
 
 namespace {
 
@@ -13,16 +14,6 @@ struct VisTable {
 };
 
 constexpr int PX = 4;   // pixels per thread
-
-// PyTorch F.interpolate(mode='bilinear', align_corners=False) source index / weight (spatial.hip)
-__device__ __forceinline__ void vis_bilinear_coord(int o, int in_size, float scale, int& i0, int& i1, float& l1) {
-    float src = ((float)o + 0.5f) * scale - 0.5f;
-    if (src < 0.f) src = 0.f;
-    i0 = (int)src;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-}
 
 __device__ __forceinline__ float clip01(float v) {
     v = (v != v) ? 0.f : v;
@@ -120,14 +111,14 @@ __global__ __launch_bounds__(256) void vis_compose_kernel(const VisTable tab, in
                         const float sy = (float)h / (float)H, sx = (float)w / (float)W;
                         int y0, y1;
                         float ly;
-                        vis_bilinear_coord(y, h, sy, y0, y1, ly);
+                        bilinear_coord(y, h, sy, y0, y1, ly);
                         int o00[PX], o01[PX], o10[PX], o11[PX];
                         float w00[PX], w01[PX], w10[PX], w11[PX];
 #pragma unroll
                         for (int j = 0; j < PX; ++j) {
                             int xa, xb;
                             float lx;
-                            vis_bilinear_coord(min(x0 + j, W - 1), w, sx, xa, xb, lx);
+                            bilinear_coord(min(x0 + j, W - 1), w, sx, xa, xb, lx);
                             o00[j] = y0 * w + xa; o01[j] = y0 * w + xb; o10[j] = y1 * w + xa; o11[j] = y1 * w + xb;
                             w00[j] = (1.f - ly) * (1.f - lx); w01[j] = (1.f - ly) * lx;
                             w10[j] = ly * (1.f - lx);         w11[j] = ly * lx;

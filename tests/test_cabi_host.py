@@ -1,6 +1,7 @@
 """Host tests of the header reader (madm_amd/_cabi.py) and of what _lib.py / _lib_data.py bind from it: the parser on
 literal snippets, one per construct and one per refusal; the struct layouts against the C compiler; a few signatures
-written out in full, so that a parser bug cannot hide behind "the binding equals the parse"."""
+written out in full, so that a parser bug cannot hide behind "the binding equals the parse"; the one loader (_cabi.load)
+against the four built libraries."""
 import ctypes
 import os
 import re
@@ -161,11 +162,76 @@ def test_the_poison_harness_wraps_what_takes_a_stream():
     assert launching == {n for n, _r, a in _lib.SYMBOLS if a and a[-1] is c_void_p and not n.startswith("madm_debug")}
 
 
-def test_a_library_of_another_abi_version_is_refused_at_import(monkeypatch):
-    from madm_amd import _lib
-    monkeypatch.setitem(_lib.ABI.constants, "MADM_ABI_VERSION", 7)
+def test_a_library_of_another_abi_version_is_refused_at_import():
+    """what _lib.py hands the loader, but for a header that declares version 7"""
     with pytest.raises(ImportError, match=r"ABI version 6, include/madm_hip.h declares 7: rebuild"):
-        _lib._load()
+        _load("hip", version=7)
+
+
+# the loader (_cabi.load) against the four built libraries, with what each _lib*.py module hands it
+class _Refused(RuntimeError):
+    pass
+
+
+LOADS = {
+    "hip": dict(header="madm_hip.h", libname="libmadm_hip.so", env="MADM_HIP_LIB", version_fn="madm_abi_version",
+                version="MADM_ABI_VERSION", version_from="include/madm_hip.h declares", last_error_fn="madm_last_error",
+                error=_Refused, no_fallback="madm_amd has no CPU fallback"),
+    "data": dict(header="madm_data.h", libname="libmadm_data.so", env="MADM_DATA_LIB", version_fn="mdata_abi_version",
+                 version=1, last_error_fn="mdata_last_error", error=_Refused, no_fallback="the dataset pipeline has no CPU fallback"),
+    "det": dict(header="madm_det.h", libname="libmadm_det.so", env="MADM_DET_LIB", version_fn="mdet_abi_version",
+                version=1, last_error_fn="mdet_last_error", error=_Refused, no_fallback="the deterministic mode has no fallback"),
+    "headfuse": dict(header="madm_headfuse.h", libname="libmadm_headfuse.so", env="MADM_HEADFUSE_LIB", version_fn="mhf_abi_version",
+                     version=1, last_error_fn="mhf_last_error", error=_Refused, no_fallback="the fused classifier has no fallback"),
+}
+
+
+def _load(which, **change):
+    """as the binding module does: the override is what its environment variable holds"""
+    kw = dict(LOADS[which], **change)
+    return _cabi.load(override=os.environ.get(kw.pop("env")), **kw)
+
+
+def _comparable(t):
+    """a ctypes type as something two parses of one header agree on: each parse makes its own struct classes"""
+    if isinstance(getattr(t, "_type_", None), type) and issubclass(t._type_, ctypes.Structure):
+        return ("pointer to", t._type_.__name__, [(n, _comparable(f)) for n, f in t._type_._fields_])
+    return t
+
+
+@pytest.mark.parametrize("which", list(LOADS))
+def test_loader_returns_the_headers_symbols_bound(which):
+    kw = LOADS[which]
+    b = _load(which)
+    fresh = _cabi.parse(os.path.join(ROOT, "include", kw["header"])).symbols()
+    norm = lambda syms: [(n, r, [_comparable(a) for a in args]) for n, r, args in syms]      # noqa: E731
+    assert b.SYMBOLS == b.ABI.symbols() and norm(b.SYMBOLS) == norm(fresh) and len(fresh) >= 3
+    assert b.LIB_PATH == (os.environ.get(kw["env"]) or os.path.join(ROOT, "madm_amd", kw["libname"]))
+    for name, restype, argtypes in b.SYMBOLS:
+        fn = getattr(b.lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    assert b.check(0, "nothing") is None and isinstance(b.last_error(), str)
+    with pytest.raises(_Refused, match=r"^some call failed \(status 3\): "):
+        b.check(3, "some call")
+
+
+@pytest.mark.parametrize("which", list(LOADS))
+def test_loader_refuses_another_abi_version(which):
+    kw = LOADS[which]
+    have = getattr(_load(which).lib, kw["version_fn"])()
+    with pytest.raises(ImportError, match=rf"{kw['libname']} has ABI version {have}, .* {have + 1}: rebuild$"):
+        _load(which, version=have + 1)
+
+
+@pytest.mark.parametrize("which", list(LOADS))
+def test_loader_names_a_missing_file_and_the_make_line(which, tmp_path, monkeypatch):
+    kw = LOADS[which]
+    missing = str(tmp_path / "nowhere" / kw["libname"])
+    monkeypatch.setenv(kw["env"], missing)
+    with pytest.raises(ImportError) as e:
+        _load(which)
+    csrc = os.path.join(ROOT, "madm_amd", "csrc")
+    assert str(e.value) == f"{missing} not found: build it with `make -C {csrc}` (or __graft_entry__.build()); {kw['no_fallback']}"
 
 
 # ---- 3. struct layouts: the ctypes classes against the compiler that built the library ----------------------------------------

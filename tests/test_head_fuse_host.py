@@ -13,17 +13,10 @@ import pytest
 import torch
 
 import head_fuse_util as hu
+import sidelib_util as su
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "madm_headfuse.h")
-
-
-def _tool(name):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 # ---- the restatement and the fixtures -------------------------------------------------------------------------------------------
@@ -135,17 +128,8 @@ def test_header_declares_only_its_own_names():
 
 
 def test_library_exports_exactly_the_header():
-    import shutil
-    from madm_amd import _cabi
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin:/opt/rocm/lib/llvm/bin")
-    if nm is None:
-        pytest.skip("no nm to list the library's exports")
     path = os.environ.get("MADM_HEADFUSE_LIB") or os.path.join(ROOT, "madm_amd", "libmadm_headfuse.so")
-    out = subprocess.run([nm, "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TtDdBb"}
-    mine = {s for s in exported if s.startswith(("mhf_", "mdet_", "madm_", "mdata_"))}
-    declared = {n for n, _r, _p in _cabi.parse(HEADER).prototypes}
-    assert mine == declared, (sorted(mine - declared), sorted(declared - mine))
+    su.assert_exports_exactly(path, "madm_headfuse.h")
 
 
 def test_import_does_not_load_the_library():
@@ -164,22 +148,11 @@ def test_import_does_not_load_the_library():
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
 
 
-class _Host:
-    """Host memory standing in for device buffers: a refused call never dereferences it."""
-
-    def __init__(self, nbytes=1 << 16):
-        self.buf = ctypes.create_string_buffer(nbytes + 64)
-        self.p = (ctypes.addressof(self.buf) + 63) & ~63
-
-    def at(self, off=0):
-        return ctypes.c_void_p(self.p + off)
-
-
 def test_bad_arguments_are_refused_without_a_gpu():
     """INVALID_ARG before any launch: null and misaligned pointers, unknown dtype, unsupported widths, H != 2h, W != 2w, row
     strides too small or off the chunk, Kp off its range -- each with the entry point's name in the message."""
     from madm_amd import _lib_headfuse as L
-    m = _Host()
+    m = su.Host()
     p = lambda i: m.at(4096 * i)      # noqa: E731
     #        dtype hd   ldh  proj  ldp w     ldw  bias  out   ldo B  h  w  H  W   C1   C2  Kp  stream
     good = [1, p(0), 256, p(1), 64, p(2), 320, p(3), p(4), 12, 2, 3, 5, 6, 10, 256, 64, 12, None]
@@ -221,15 +194,6 @@ def test_bad_arguments_are_refused_without_a_gpu():
 
 
 def test_headfuse_kernels_use_no_scratch_and_no_packed_fp32():
-    import shutil
     from madm_amd._lib_headfuse import LIB_PATH
-    scratch, pk = _tool("scratch_scan"), _tool("isa_pk_scan")
-    if not (os.path.exists(scratch.READELF) or shutil.which(scratch.READELF)) or \
-            not (os.path.exists(pk.OBJDUMP) or shutil.which(pk.OBJDUMP)):
-        pytest.skip("llvm-readelf / llvm-objdump of the ROCm toolchain not found")
-    rows = scratch.kernels(LIB_PATH)
+    rows = su.scan_kernels(LIB_PATH)
     assert len(rows) == 9 and all("upsample_cat_classify_kernel" in k for k in rows), sorted(rows)    # 3 dtypes x 3 class-tile counts
-    bad = {k: v for k, v in rows.items() if v.get("private_segment_fixed_size", 0) > 0 or v.get("vgpr_spill_count", 0) > 0}
-    assert not bad, f"kernels with scratch: {bad}"
-    total, low, per = pk.scan(LIB_PATH)
-    assert total == 0 and low == 0 and not per, f"packed-FP32 ops in libmadm_headfuse.so: {per}"
