@@ -1,5 +1,5 @@
-"""Reader of the C ABI headers (include/madm_hip.h, madm_data.h, madm_det.h, madm_headfuse.h): the ctypes structures,
-signatures and constants that ``_lib.py`` / ``_lib_data.py`` / ``_lib_det.py`` / ``_lib_headfuse.py`` bind come from the text
+"""Reader of the C ABI headers (include/madm_hip.h, madm_data.h, madm_det.h, madm_headfuse.h, madm_wslab.h): the ctypes structures,
+signatures and constants that ``_lib.py`` / ``_lib_data.py`` / ``_lib_det.py`` / ``_lib_headfuse.py`` / ``_lib_wslab.py`` bind come from the text
 every ``.hip`` file is compiled against, not from a table kept next to it.  Standard library only: no torch; ``parse``
 loads no library (tools/conv_plan_fixture.py and the host tests use it on their own), ``load`` at the end is the one
 loader the binding modules share.
@@ -145,7 +145,7 @@ def parse_packaged(name):
 
 
 def load(header, libname, override, version_fn, version, last_error_fn, error, no_fallback, version_from="this binding is for"):
-    """The one loader behind ``_lib.py``, ``_lib_data.py``, ``_lib_det.py`` and ``_lib_headfuse.py``: binds madm_amd/<libname>,
+    """The one loader behind ``_lib.py``, ``_lib_data.py``, ``_lib_det.py``, ``_lib_headfuse.py`` and ``_lib_wslab.py``: binds madm_amd/<libname>,
     or the file ``override`` names (what the module's MADM_*_LIB environment variable holds), from include/<header>.  Returns a
     namespace of ABI (the parsed header), SYMBOLS (``ABI.symbols()``), LIB_PATH, lib (every declared symbol typed),
     last_error() and check(rc, what), which raises ``error`` with the library's text on a non-zero status.  ``version`` is

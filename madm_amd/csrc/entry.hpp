@@ -1,4 +1,4 @@
-// Host scaffolding of a side library's entry points (data.hip, det.hip, headfuse.hip): the thread's last error text, the
+// Host scaffolding of a side library's entry points (data.hip, det.hip, headfuse.hip, wslab.hip): the thread's last error text, the
 // launch check and the argument check.  Everything here has internal linkage -- each library is one object and exports
 // exactly what its header declares -- and nothing depends on include/madm_hip.h.  Every status enum has OK == 0; the
 // library passes its own codes, and keeps a one-line  #define Mxx_REQUIRE(...) ENTRY_REQUIRE(Mxx_ERR_INVALID_ARG, __VA_ARGS__).

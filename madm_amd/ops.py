@@ -198,22 +198,38 @@ class _Prof:
 # conv2d_wgrad runs with one pixel slice (a sole owner per dw tile).  DESIGN.md section 24 has the site table, what is left as
 # it is (f64 accumulation of f32 block partials) and what the mode costs.  With more than one rank the mode fixes each
 # rank's own arithmetic; the order inside the gradient all-reduce is the collective library's.
+#
+# ``"slabs"`` next to ``True`` is the same mode with ONE difference: conv2d_wgrad keeps its pixel slices -- each slice stores
+# its partial tiles to a slab of the workspace, a fold adds the slabs in index order (libmadm_wslab.so, include/madm_wslab.h;
+# loaded by the first weight gradient that takes this path).  ``True`` stays what it was, bit for bit.
 _DETERMINISTIC = False
+_WGRAD_SLABS = False     # only ever set together with _DETERMINISTIC
 _det = None
+_wslab = None
 
 
 def set_deterministic(flag):
-    """Switches the fixed-order gradient reductions on or off for the whole process; returns the previous value."""
-    global _DETERMINISTIC, _det
+    """Switches the fixed-order gradient reductions on or off for the whole process; returns the previous value (False, True
+    or "slabs": what was passed in).  ``"slabs"``: the mode with the ordered-slab weight gradient."""
+    global _DETERMINISTIC, _WGRAD_SLABS, _det
+    if isinstance(flag, str) and flag != "slabs":
+        raise ValueError(f"set_deterministic takes False, True or 'slabs', got {flag!r}")
     if flag and _det is None:
         from . import _lib_det
         _det = _lib_det
-    prev, _DETERMINISTIC = _DETERMINISTIC, bool(flag)
+    prev = "slabs" if _WGRAD_SLABS else _DETERMINISTIC
+    _DETERMINISTIC, _WGRAD_SLABS = bool(flag), isinstance(flag, str)
     return prev
 
 
 def is_deterministic():
     return _DETERMINISTIC
+
+
+def wgrad_path():
+    """The weight-gradient path ``conv2d_wgrad`` takes without an explicit ``slabs=``: "atomic" (default mode: pixel slices
+    added with float atomics), "one_slice" (deterministic mode True) or "slabs" (deterministic mode "slabs")."""
+    return "slabs" if _WGRAD_SLABS else ("one_slice" if _DETERMINISTIC else "atomic")
 
 
 class deterministic:
@@ -379,11 +395,13 @@ def linear(x, w, *, bias=None, residual=None, epilogue=EPI_NONE, out=None, x2=No
 
 
 def conv2d_wgrad(x1, dout, B, IH, IW, *, x2=None, KH=1, KW=1, stride=1, pad_t=0, pad_l=0, OH=None, OW=None,
-                 upsample=False, dw=None, splitm=0, dbias=None):
+                 upsample=False, dw=None, splitm=0, dbias=None, slabs=None):
     """Weight gradient of :func:`conv2d` (torch autograd in the reference, engine/train_loop.py:203-217):
     dw[n][(kh, kw, c)] += sum_m dout[m][n] * A(m, k).  x1 / x2: the tensors the forward conv read; dout: [B*OH*OW, N];
     dw: f32 [N, KH*KW*(C1+C2)], ACCUMULATED into (a zeroed one is created when None); dbias: None or f32 [N], accumulated
-    into: the column sums of dout (the bias gradient), gathered by the same launch."""
+    into: the column sums of dout (the bias gradient), gathered by the same launch.
+    ``slabs``: None follows the mode (``wgrad_path()``); an int > 0 forces the ordered-slab path of libmadm_wslab.so with that
+    many pixel slices, whatever the mode (tests and tools)."""
     _need_cuda(x1, x2, dout, dw)
     C1 = x1.shape[1]
     C2 = 0 if x2 is None else x2.shape[1]
@@ -398,7 +416,23 @@ def conv2d_wgrad(x1, dout, B, IH, IW, *, x2=None, KH=1, KW=1, stride=1, pad_t=0,
     if dw is None:
         dw = zeros_f32((N, K), x1.device)
     assert dw.dtype == torch.float32 and dw.is_contiguous() and tuple(dw.shape) == (N, K)
-    a = _lib.Conv2dWgradArgs()
+    if slabs is None:
+        slabs = 0 if _WGRAD_SLABS else None
+    elif int(slabs) <= 0:
+        raise ValueError(f"conv2d_wgrad: slabs must be None or an int > 0, got {slabs!r}")
+    if dbias is not None:
+        _need_cuda(dbias)
+        assert dbias.dtype == torch.float32 and dbias.is_contiguous() and dbias.numel() == N
+    if slabs is None:
+        a = _lib.Conv2dWgradArgs()
+        a.splitm = 1 if _DETERMINISTIC else int(splitm)   # one pixel slice: a sole owner per dw tile, one add per dbias address
+    else:
+        global _wslab
+        if _wslab is None:
+            from . import _lib_wslab
+            _wslab = _lib_wslab
+        a = _wslab.Conv2dWgradArgs()
+        a.slices = int(slabs)
     a.dtype = dtype_code(x1)
     a.in1 = x1.data_ptr()
     a.in2 = x2.data_ptr() if x2 is not None else None
@@ -411,19 +445,28 @@ def conv2d_wgrad(x1, dout, B, IH, IW, *, x2=None, KH=1, KW=1, stride=1, pad_t=0,
     a.KH, a.KW, a.stride, a.pad_t, a.pad_l = KH, KW, stride, pad_t, pad_l
     a.upsample = 1 if upsample else 0
     a.N = N
-    a.splitm = 1 if _DETERMINISTIC else int(splitm)   # one pixel slice: a sole owner per dw tile, one add per dbias address
     if dbias is not None:
-        _need_cuda(dbias)
-        assert dbias.dtype == torch.float32 and dbias.is_contiguous() and dbias.numel() == N
         a.dbias = dbias.data_ptr()
+    if slabs is None:
+        def launch():
+            check(lib.madm_conv2d_wgrad(ctypes.byref(a), _stream()), "madm_conv2d_wgrad")
+    else:   # the slabs of this launch in the stream's workspace: written by the slab kernel, read by the fold behind it
+        nbytes_ws = int(_wslab.lib.mws_conv2d_wgrad_workspace_bytes(ctypes.byref(a)))
+        if nbytes_ws == 0:
+            raise ValueError("conv2d_wgrad: mws_conv2d_wgrad_workspace_bytes refuses these sizes")
+        ws = _workspace(nbytes_ws, x1.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+
+        def launch():
+            _wslab.check(_wslab.lib.mws_conv2d_wgrad(ctypes.byref(a), _stream()), "mws_conv2d_wgrad")
     if PROFILE is None:
-        check(lib.madm_conv2d_wgrad(ctypes.byref(a), _stream()), "madm_conv2d_wgrad")
+        launch()
     else:
         es = x1.element_size()
         nbytes = B * IH * IW * (C1 + C2) * es + dout.numel() * es + dw.numel() * 4
         with _Prof("conv2d_wgrad" + _SUFFIX[x1.dtype], 2.0 * dout.shape[0] * N * K,
                    f"M{dout.shape[0]} N{N} K{K} k{KH} s{stride}", nbytes):
-            check(lib.madm_conv2d_wgrad(ctypes.byref(a), _stream()), "madm_conv2d_wgrad")
+            launch()
     return dw
 
 

@@ -25,7 +25,10 @@ class MadmTrainer:
                  amp=True, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000,
                  lr_multiplier=None, exchange="allreduce", wire_dtype=None, deterministic=False):
         self.model = model
-        self.deterministic = bool(deterministic)   # run_step under ops.deterministic(): see that docstring
+        # run_step under ops.deterministic(): see that docstring.  False, True or "slabs" (the ordered-slab weight gradient)
+        if isinstance(deterministic, str) and deterministic != "slabs":
+            raise ValueError(f"deterministic takes False, True or 'slabs', got {deterministic!r}")
+        self.deterministic = deterministic if isinstance(deterministic, str) else bool(deterministic)
         try:      # the extractor whose per-pass range assert this trainer defers to the end of its step
             self._ldm = model.backbone.feature_extractor.ldm_extractor
         except AttributeError:
@@ -137,10 +140,11 @@ class MadmTrainer:
         (forward, backward, optimizer) runs in ``ops.deterministic()`` mode -- every f32 accumulation of this rank's step in
         a fixed order, so that two runs from the same state give the same bits -- and the previous value of the switch is
         restored afterwards, also when the step raises.  With more than one rank this fixes each rank's own arithmetic; the
-        order inside the gradient all-reduce is the collective library's."""
+        order inside the gradient all-reduce is the collective library's.  ``deterministic="slabs"`` is the same mode with the
+        ordered-slab weight gradient (``ops.set_deterministic``): reproducible as well, other low-order bits than ``True``."""
         if not self.deterministic:
             return self._run_step(data)
-        with ops.deterministic():
+        with ops.deterministic(self.deterministic):
             return self._run_step(data)
 
     def _run_step(self, data):
