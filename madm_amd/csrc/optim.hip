@@ -85,15 +85,19 @@ __global__ __launch_bounds__(256) void adamw_table_kernel(float* __restrict__ p,
 __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, size_t n,
                                                   float alpha) {
     const size_t n4 = n / 4;
+    // the function: a = alpha as passed (f32), b = 1 - a in f32 (exact for a >= 1/2; a + b == 1 always), e' = fma(a, e, fl(b q)).
+    // With the product a e unrounded a teacher equal to its student stays equal bit for bit (a x + fl(b x) lies within half an
+    // ulp of b x of x); the FMA is spelled out so that this does not hang on the compiler's contraction (a rounded a e loses it).
     const float b = 1.f - alpha;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         float4 e = reinterpret_cast<float4*>(ema)[i];
         const float4 q = reinterpret_cast<const float4*>(p)[i];
-        e.x = alpha * e.x + b * q.x; e.y = alpha * e.y + b * q.y; e.z = alpha * e.z + b * q.z; e.w = alpha * e.w + b * q.w;
+        e.x = fmaf(alpha, e.x, b * q.x); e.y = fmaf(alpha, e.y, b * q.y);
+        e.z = fmaf(alpha, e.z, b * q.z); e.w = fmaf(alpha, e.w, b * q.w);
         reinterpret_cast<float4*>(ema)[i] = e;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (size_t i = n4 * 4; i < n; ++i) ema[i] = alpha * ema[i] + b * p[i];
+        for (size_t i = n4 * 4; i < n; ++i) ema[i] = fmaf(alpha, ema[i], b * p[i]);
 }
 
 // fingerprint of one element: a 64-bit mix of (global index, bit pattern); all arithmetic modulo 2^64

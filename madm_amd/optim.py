@@ -220,7 +220,9 @@ class EmaPairs:
             if spans:
                 lt, ls, lb = spans[-1]
                 gap = tp - (lt + lb)
-                if 0 <= gap < 4096 and sp - (ls + lb) == gap and (lb + gap) % 4 == 0:   # same (zero) padding on both sides
+                # the same (zero) padding on both sides, and less than one 16-byte slot of it: a wider gap can hold a whole
+                # tensor of a flat buffer (one that is not in the pair list), which a span across it would overwrite
+                if 0 <= gap < 16 and sp - (ls + lb) == gap and (lb + gap) % 4 == 0:
                     spans[-1][2] = lb + gap + nb
                     continue
             spans.append([tp, sp, nb])

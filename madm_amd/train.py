@@ -17,6 +17,18 @@ from . import ops, optim
 from .dist import GradBucketReducer
 
 
+def next_loss_scale(scale, tracker, stepped, growth_factor, backoff_factor, growth_interval):
+    """torch.cuda.amp.GradScaler.update as a pure function: (scale, growth tracker) after a step that was taken
+    (``stepped``) or skipped on a non-finite gradient norm.  A skip backs the scale off and restarts the count of
+    consecutive good steps; the ``growth_interval``-th good step in a row grows it and restarts the count as well."""
+    if not stepped:
+        return scale * backoff_factor, 0
+    tracker += 1
+    if tracker == growth_interval:
+        return scale * growth_factor, 0
+    return scale, tracker
+
+
 class MadmTrainer:
     """One process per GPU.  ``dist``: an initialised torch.distributed module (backend nccl == RCCL, or gloo) or None.
     At construction rank 0's parameters are broadcast (DistributedDataParallel's start-up contract, main.py:289-294)."""
@@ -197,14 +209,8 @@ class MadmTrainer:
 
         norm, stepped = self.opt.step(clip_grad=self.grad_clip, loss_scale=self.scale, touched=touched, on_synced=check_probes)
         if self.amp:
-            if not stepped:
-                self.scale *= self.backoff_factor
-                self._growth_tracker = 0
-            else:
-                self._growth_tracker += 1
-                if self._growth_tracker == self.growth_interval:
-                    self.scale *= self.growth_factor
-                    self._growth_tracker = 0
+            self.scale, self._growth_tracker = next_loss_scale(self.scale, self._growth_tracker, stepped, self.growth_factor,
+                                                               self.backoff_factor, self.growth_interval)
         self.iter += 1
         if ev is not None:      # all-reduce time the compute stream had to WAIT for after the backward (the exposed part)
             ev[1].synchronize()
