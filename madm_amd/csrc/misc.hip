@@ -4,31 +4,43 @@
 
 namespace {
 
-// one atomicMin/atomicMax pair per BLOCK (thousands of waves hammering two addresses serialise)
-__device__ __forceinline__ void block_minmax(float lo, float hi, float* minmax) {
+// one atomicMin/atomicMax pair per BLOCK (thousands of waves hammering two addresses serialise).  `nan`: the thread saw a NaN
+// (fminf / fmaxf drop it); folded with the reduction, and a block that saw one publishes (NaN, NaN), which fails the caller's
+// -1 <= lo && hi <= 1 exactly as the reference's assert on torch.min / torch.max does (ldm_diffusers.py:147).
+__device__ __forceinline__ void block_minmax(float lo, float hi, bool nan, float* minmax) {
     __shared__ float s_lo[4], s_hi[4];
+    __shared__ int s_nan[4];
+    int bad = nan ? 1 : 0;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         lo = fminf(lo, __shfl_xor(lo, o));
         hi = fmaxf(hi, __shfl_xor(hi, o));
+        bad |= __shfl_xor(bad, o);
     }
     const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_lo[w] = lo; s_hi[w] = hi; }
+    if ((threadIdx.x & 63) == 0) { s_lo[w] = lo; s_hi[w] = hi; s_nan[w] = bad; }
     __syncthreads();
     if (threadIdx.x == 0) {
         const int nw = (blockDim.x + 63) >> 6;
-        for (int i = 1; i < nw; ++i) { lo = fminf(lo, s_lo[i]); hi = fmaxf(hi, s_hi[i]); }
-        // Native integer atomics on the float bit patterns (sign-aware: for v >= 0 the signed-int order is the float
-        // order, for v < 0 the unsigned order is the reversed float order).  atomicMin/Max(float*) compile to CAS
-        // loops: with the first ~2000 resident blocks all improving the freshly reset bound they serialised into
-        // ~0.5 ms per call.  A block that cannot improve the published bound skips its atomic altogether.
-        if (lo <= hi) {
+        for (int i = 1; i < nw; ++i) { lo = fminf(lo, s_lo[i]); hi = fmaxf(hi, s_hi[i]); bad |= s_nan[i]; }
+        // Native integer atomics on the float bit patterns, chosen by the SIGN BIT (-0.0 counts as negative: its pattern is
+        // INT_MIN, which a signed max could never publish and a signed min would publish over everything): with the sign bit
+        // clear the signed-int order is the float order, with it set the unsigned order is the reversed float order.
+        // atomicMin/Max(float*) compile to CAS loops: with the first ~2000 resident blocks all improving the freshly reset
+        // bound they serialised into ~0.5 ms per call.  A block that cannot improve the published bound skips its atomic.
+        if (bad) {
+            // sticky under every atomic below: 0xffc00000 is above every negative float's pattern (unsigned max) and below
+            // every non-negative one's (signed min); 0x7fc00000 is above every non-negative pattern (signed max) and below
+            // every negative one's (unsigned min); a comparison with the NaN already there makes the other blocks skip
+            atomicMax(reinterpret_cast<unsigned*>(&minmax[0]), 0xffc00000u);
+            atomicMax(reinterpret_cast<int*>(&minmax[1]), 0x7fc00000);
+        } else if (lo <= hi) {
             if (lo < __builtin_nontemporal_load(&minmax[0])) {
-                if (lo >= 0.f) atomicMin(reinterpret_cast<int*>(&minmax[0]), __float_as_int(lo));
+                if (__float_as_int(lo) >= 0) atomicMin(reinterpret_cast<int*>(&minmax[0]), __float_as_int(lo));
                 else atomicMax(reinterpret_cast<unsigned*>(&minmax[0]), __float_as_uint(lo));
             }
             if (hi > __builtin_nontemporal_load(&minmax[1])) {
-                if (hi >= 0.f) atomicMax(reinterpret_cast<int*>(&minmax[1]), __float_as_int(hi));
+                if (__float_as_int(hi) >= 0) atomicMax(reinterpret_cast<int*>(&minmax[1]), __float_as_int(hi));
                 else atomicMin(reinterpret_cast<unsigned*>(&minmax[1]), __float_as_uint(hi));
             }
         }
@@ -42,6 +54,7 @@ __device__ __forceinline__ void block_minmax(float lo, float hi, float* minmax) 
 __global__ __launch_bounds__(256) void range_probe_kernel(const float* __restrict__ x, size_t n, float mean,
                                                           float inv_std, float* minmax) {
     float lo = INFINITY, hi = -INFINITY;
+    bool nan = false;                 // unordered compares (two per float4) on the registers already loaded: no memory traffic
     const size_t n4 = n / 4;
     // min / max commute with the (monotone) normalisation: taken on the raw values, normalised once at the end; eight loads
     // in flight per thread (one load per trip: 24 dependent ~0.5 us round trips = the 12 us this kernel took for a 6 MB batch)
@@ -53,12 +66,14 @@ __global__ __launch_bounds__(256) void range_probe_kernel(const float* __restric
         for (int u = 0; u < 8; ++u) v[u] = reinterpret_cast<const float4*>(x)[i + u * stride];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
+            nan |= __builtin_isunordered(v[u].x, v[u].y) | __builtin_isunordered(v[u].z, v[u].w);
             lo = fminf(fminf(lo, v[u].x), fminf(fminf(v[u].y, v[u].z), v[u].w));
             hi = fmaxf(fmaxf(hi, v[u].x), fmaxf(fmaxf(v[u].y, v[u].z), v[u].w));
         }
     }
     for (; i < n4; i += stride) {
         const float4 v = reinterpret_cast<const float4*>(x)[i];
+        nan |= __builtin_isunordered(v.x, v.y) | __builtin_isunordered(v.z, v.w);
         lo = fminf(fminf(lo, v.x), fminf(fminf(v.y, v.z), v.w));
         hi = fmaxf(fmaxf(hi, v.x), fmaxf(fmaxf(v.y, v.z), v.w));
     }
@@ -68,10 +83,11 @@ __global__ __launch_bounds__(256) void range_probe_kernel(const float* __restric
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const float a = (x[n4 * 4 + threadIdx.x] - mean) * inv_std;
+        nan |= (a != a);
         lo = fminf(lo, a);
         hi = fmaxf(hi, a);
     }
-    block_minmax(lo, hi, minmax);
+    block_minmax(lo, hi, nan, minmax);
 }
 
 // NCHW f32 image -> channels-last dtype, (x - mean) / std in the first C channels, zeros above.
